@@ -10,9 +10,13 @@ forward on chosen+rejected (4 decoder forwards per pair) -> fused LM-head log-pr
 -> backward through the policy only -> (RCCL gradient all-reduce, N > 1) -> global-norm clip + AdamW
 + cosine warm-up.  Inputs are synthetic and resident in HBM before the timed region.
 
-Output: ONE JSON line on rank 0 with the contract's keys plus
-  "roofline":     dominant kernel (forward NN MFMA GEMM) TFLOP/s from HIP events on its launch stream
+Output: ONE JSON line on rank 0 with the contract's keys.  A plain run sets up, warms up, times the steps and prints it;
+``--full`` adds what takes measurements of its own:
+  "roofline":     dominant kernel (forward NN MFMA GEMM) TFLOP/s from HIP events on its launch stream, beside the
+                  library GEMM ceiling measured on the same GPU
   "cpu_baseline": the oracle restatement timed on this box's host cores on a bounded sample.
+``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy (float32; a fixed, seeded sample of
+the parameters and gradients), so that two builds can be compared output for output on identical seeded inputs.
 """
 from __future__ import annotations
 
@@ -149,6 +153,44 @@ def pmc_from_profile(pairs_per_gpu: int, kernel_substr: str):
     return None
 
 
+DUMP_SAMPLE = 1 << 20   # elements per parameter / gradient sample (4 MiB): at most 4 trained segments -> 32 MiB
+DUMP_LIMIT = 64 << 20
+
+
+def step_outputs(loss, step, ref, ws, opt, segs, nseq: int, dpo: bool) -> dict:
+    """What a caller of the timed step receives, as host float32 arrays: the loss; Stage 2's DPO metrics and per-sequence
+    log-probs (chosen rows, then rejected) of the policy and the reference; the optimizer's control block (grad norm,
+    finite flag, clip factor, lr, bias corrections, step counters); per trained segment the updated master weights and the
+    step's gradients, whole or at a fixed seeded sample of DUMP_SAMPLE flat positions."""
+    out = {"loss": loss.reshape(1)}
+    if dpo:
+        out["dpo_metrics"] = step.metrics
+        out["policy_seq_logprob"] = ws.bufs["pol.seq_lp"][:nseq]
+        if ref is not None:
+            out["reference_seq_logprob"] = ws.bufs["ref.seq_lp"][:nseq]
+    out["optimizer_ctrl"] = opt.ctrl
+    g = torch.Generator().manual_seed(0)
+    for s in segs:
+        idx = None
+        if s.numel > DUMP_SAMPLE:
+            idx = torch.randint(0, s.numel, (DUMP_SAMPLE,), generator=g).sort().values.to(s.fp32.device)
+        for kind, buf in (("param", s.fp32), ("grad", s.grad)):
+            out[f"{s.name}_{kind}"] = buf if idx is None else buf[idx]
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> int:
+    """Writes every array as ``out_dir/<name>.npy``; returns the bytes written (at most DUMP_LIMIT)."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return total
+
+
 def self_launch(n: int, argv, timeout_s: float) -> int:
     """``python bench.py --gpus N`` started as ONE plain process (how the driver starts ``--gpus 1``): spawn the N ranks
     here, as fresh children of a parent that has not touched the GPU (no HIP call, no ``torch.cuda.*``) - one
@@ -221,6 +263,11 @@ def main():
     ap.add_argument("--launch-timeout", type=float, default=3000.0, help="self-launched job limit in seconds")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the dominant GEMM's roofline (HIP events "
+                         "around its launches in the timed steps), the library GEMM ceiling and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
     ap.add_argument("--pairs-per-gpu", type=int, default=512,
                     help="preference pairs per GPU per optimizer step (rounds 1-2 ran 128 / 256 on padded rows; with packed "
                          "rows 512 pairs are ~75 k token rows per GEMM and ~90 of the 288 GB: +5 %% pairs/s over 256)")
@@ -231,9 +278,9 @@ def main():
     ap.add_argument("--vision-model", default="openai/clip-vit-base-patch32")
     ap.add_argument("--text-model", default="gpt2-medium")
     ap.add_argument("--reference-free", action="store_true", help="2-forward trainer path instead of 4-forward DPO")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-pairs", type=int, default=8, help="pairs per CPU-baseline step (BASELINE.md section 3: 8)")
-    ap.add_argument("--no-probe", action="store_true")
+    ap.add_argument("--no-probe", action="store_true", help="--full without the roofline probe")
     ap.add_argument("--dropout", type=float, default=0.1, help="train-mode dropout of the policy (reference: 0.1)")
     ap.add_argument("--with-input-path", action="store_true",
                     help="feed every step from HOST batches through the input path (pinned staging, async H2D, device-side "
@@ -343,7 +390,7 @@ def main():
         batches = [prep(r, dev) for r in raw]
 
     probe = GemmProbe(hip.NN)
-    if not args.no_probe and dp.rank == 0:
+    if args.full and not args.no_probe and dp.rank == 0:
         hip.gemm_probe = probe
 
     last = [None]
@@ -384,6 +431,10 @@ def main():
         loss_t = dp.all_reduce_sum(loss_t) / dp.world
     loss_val = float(loss_t)
     st = opt.state()
+    if args.dump_outputs and dp.rank == 0:
+        outs = step_outputs(last[0], step, ref, model.ws, opt, segs, 2 * B, not stage1)
+        log(f"outputs of the last timed step: {dump_outputs(args.dump_outputs, outs) / 2 ** 20:.1f} MiB "
+            f"in {len(outs)} arrays -> {args.dump_outputs}")
 
     if dp.rank == 0:
         pairs = B * dp.world * args.steps
@@ -502,7 +553,7 @@ def main():
                 del xa, xb
             except Exception as exc:  # noqa: BLE001 - a missing BLAS must not break the bench line
                 res["roofline"]["library_ceiling_note"] = f"unavailable: {exc}"
-        if dp.world == 1 and not args.no_cpu_baseline and not stage1:
+        if args.full and dp.world == 1 and not args.no_cpu_baseline and not stage1:
             hip.gemm_probe = None
             log("cpu baseline (oracle on host cores) ...")
             res["cpu_baseline"] = cpu_baseline(model, arch, S, beta, args.cpu_pairs)
