@@ -93,9 +93,10 @@ typedef struct pgca_gemm_args {
   int32_t ld_aux;
   /* ROWSTATS / DLOGITS */
   const int64_t* targets; /* [M] column index per row, or NULL (NT-Xent: diagonal given explicitly) */
-  float* stat_max;        /* [M, stat_ld]  partial row max   (ROWSTATS) */
+  float* stat_max;        /* [M, stat_ld]  partial row max   (ROWSTATS), one per 64-column strip */
   float* stat_sum;        /* [M, stat_ld]  partial sum exp(v - max) */
-  int32_t stat_ld;        /* >= 2 * ceil(N / 128) */
+  int32_t stat_ld;        /* >= 2 * ceil(N / 128); both tile sizes write exactly columns [0, 2 * ceil(N / 128)) of a
+                             row ((-inf, 0) for a strip wholly past N) and nothing beyond */
   float* target_val;      /* [M] v at the target column (ROWSTATS) */
   const float* row_lse;   /* [M] (DLOGITS) */
   const float* row_scale; /* [M] (DLOGITS) */

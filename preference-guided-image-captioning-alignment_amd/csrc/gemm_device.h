@@ -131,6 +131,10 @@ __device__ __forceinline__ void epilogue_rowstats(const pgca_gemm_args& a, f32x4
   const int rbase = m0 + wm * 64 + (lane >> 4) * 4;
   const int cbase = n0 + wn * 64 + (lane & 15);
   const int part = (n0 >> 6) + wn;  // one partial per 64-column strip
+  // The stat_ld contract is 2 * ceil(N / 128) partials per row, the 128^2 tile's count.  A 256^2 tile writes four strips,
+  // so its last column tile can reach two strips further when N mod 256 is in 1..128: those would land on parts 0 and 1 of
+  // the next row (and past the buffer on the last row).  Strips wholly past N but inside the range still write (-inf, 0).
+  const bool part_ok = part < 2 * ((a.N + 127) >> 7);
   // the 16 target ids of this lane's rows, requested before anything depends on them (one round trip, not 16)
   long long tg[4][4];
 #pragma unroll
@@ -161,7 +165,7 @@ __device__ __forceinline__ void epilogue_rowstats(const pgca_gemm_args& a, f32x4
       float sm = 0.f;
       if (mx > -INFINITY) sm = __expf(x[0] - mx) + __expf(x[1] - mx) + __expf(x[2] - mx) + __expf(x[3] - mx);
       sm = row16_sum(sm);
-      if ((lane & 15) == 0 && row < a.M) {
+      if ((lane & 15) == 0 && row < a.M && part_ok) {
         a.stat_max[(size_t)row * a.stat_ld + part] = mx;
         a.stat_sum[(size_t)row * a.stat_ld + part] = sm;
       }

@@ -91,7 +91,9 @@ def test_full_depth_c2_stage2_four_forward(full_c2):
     d_ref = float(((rlp - want_ref) / cnt).abs().max())
     print(f"full depth C2 stage 2: per-token-mean log-prob |d| policy {d_pol:.2e} reference {d_ref:.2e}; "
           f"loss {loss:.5f} vs {float(ref_loss):.5f}")
-    assert d_pol <= 2e-2 and d_ref <= 2e-2, (d_pol, d_ref)
+    # measured 1.90e-3 / 1.61e-3 (2.58e-3 / 3.37e-3 before the LM-head ROWSTATS overrun fix): ~3x the measured value,
+    # tighter than SURVEY 8(d)'s 2e-2
+    assert d_pol <= 6e-3 and d_ref <= 6e-3, (d_pol, d_ref)
     assert abs(loss - float(ref_loss)) <= 5e-3, (loss, float(ref_loss))
     dec = "caption_decoder.lm_model.transformer."
     worst = 1.0

@@ -152,7 +152,17 @@ def test_gemm_derivative_epilogues_residual_accumulate(hip, tile):
 def test_lm_head_rowstats_and_dlogits(hip, tile):
     """Fused LM head: log-prob gather without logits in HBM (model.py:1069-1079), and the
     recomputed dlogits = g * (softmax - onehot)."""
-    M, V, K = 150, 1004, 128          # V not a multiple of 8 or of the 128 tile
+    lm_head_rowstats_and_dlogits(hip, 1004)   # V not a multiple of 8 or of the 128 tile
+
+
+def test_lm_head_rowstats_and_dlogits_partial_last_tile(hip, tile):
+    """V mod 256 in 1..128 (GPT-2's 50257 is 81): the last 256^2 column tile has two 64-column strips past
+    2 * ceil(V / 128), which must not be written (stat_ld is exactly that count here)."""
+    lm_head_rowstats_and_dlogits(hip, 850)
+
+
+def lm_head_rowstats_and_dlogits(hip, V):
+    M, K = 150, 128
     Vp = (V + 127) // 128 * 128
     h = rnd(M, K, seed=1, scale=0.5).bfloat16()
     wte = torch.zeros(Vp, K, dtype=torch.bfloat16, device=dev())
