@@ -223,7 +223,14 @@ int pgca_colsum(const void* x_bf16, const float* x_f32, int32_t M, int32_t N, in
  * qkv / out / dout / dqkv and has min(cu[b+1]-cu[b], S) tokens (a KV-cache decode step passes the cache stride in cu and
  * the filled length as S, with no mask, lse or dropout); in training S stays the PADDED length: key_mask, lse and the dropout index
  * keep their [B, S] geometry, so the result of every real token equals the padded launch's.  Padding positions of the
- * reference batch (model.py:1069-1083 zeroes their loss terms, :449-456 their pooling weight) are then never computed. */
+ * reference batch (model.py:1069-1083 zeroes their loss terms, :449-456 their pooling weight) are then never computed.
+ * What is written: every row of out / dqkv that belongs to a sequence (packed: rows cu[b] .. cu[b] + len - 1, the filler
+ * pseudo-sequences included; padded: all B*S rows, padding positions too) and the lse slots [b, h, t] with t < len; lse
+ * slots beyond a packed sequence's length and rows outside every sequence are NEVER touched.
+ * A query with NO allowed key (key_mask zero at every key up to the causal edge, e.g. a hole at position 0) gets
+ * out = 0, lse = -inf and carries no gradient: its dq row is 0 and it adds nothing to dk / dv - the same in the one-tile
+ * forward, the key-tiled forward and the backward.  (The reference's additive finfo.min bias would average ALL S keys
+ * for such a row; right-padded captions, model.py:1069-1083, never contain one.) */
 #define PGCA_ATTN_MAX_S 512
 int pgca_attention_fwd(const void* qkv, const int32_t* key_mask, int32_t B, int32_t S, int32_t heads,
                        int32_t causal, void* out, float* lse, uint32_t drop_seed, uint32_t drop_threshold,
