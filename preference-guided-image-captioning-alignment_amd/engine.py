@@ -12,8 +12,10 @@ Reference call sites replaced are cited per method.
 """
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -36,6 +38,7 @@ class Workspace:
     def __init__(self, device):
         self.device = torch.device(device)
         self.bufs: Dict[str, torch.Tensor] = {}
+        self._stamps: Dict[str, tuple] = {}
 
     def get(self, key: str, shape, dtype, zero: bool = False) -> torch.Tensor:
         shape = tuple(int(s) for s in shape)
@@ -51,6 +54,13 @@ class Workspace:
         if zero:
             v.zero_()
         return v
+
+    def cached(self, key: str, stamp: tuple, make) -> torch.Tensor:
+        """Derived tensor (an index vector) kept under ``key``: ``make()`` builds it again only when ``stamp`` changes."""
+        if key not in self.bufs or self._stamps.get(key) != stamp:
+            self.bufs[key] = make()
+            self._stamps[key] = stamp
+        return self.bufs[key]
 
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.bufs.values())
@@ -284,17 +294,53 @@ def _ln_param_grads(part: torch.Tensor, nb: int, H: int, *outs: torch.Tensor) ->
     hip.colsum_finish4(part, len(outs), nb, H, outs, accumulate=True)
 
 
+def _rows(pack: Optional[RowPack], Bq: int, S: int) -> SimpleNamespace:
+    """Row layout of a launch over a [Bq, S] batch - every padded position or, with ``pack``, its packed rows only:
+    ``M`` rows of the residual stream, ``cu`` first row of each sequence, ``ids`` padded position of each row (what the
+    dropout sites hash), ``nseq`` sequences of an attention launch (the packed filler adds some), ``embed`` the row
+    keywords of ``hip.embed_fwd``."""
+    if pack is None:
+        return SimpleNamespace(M=Bq * S, cu=None, ids=None, nseq=Bq, embed={})
+    return SimpleNamespace(M=pack.Mp, cu=pack.cu, ids=pack.row_ids, nseq=pack.nseq,
+                           embed=dict(row_ids=pack.row_ids, n_rows=pack.Mp))
+
+
+def _dsite(drop, layer: int, kind: int):
+    """Dropout triple of one site from a ``DropoutPlan.bind`` closure; None when the forward runs without dropout."""
+    return drop(layer, kind) if drop is not None else None
+
+
 class _P:
     """Resolved views of one parameter: f32 master, bf16 mirror, gradient (if trainable)."""
     __slots__ = ("w", "b", "g")
 
-    def __init__(self, seg: Segment, name: str):
-        self.w = seg.w(name)
-        self.b = seg.wb(name) if seg.bf16 is not None else None
-        self.g = seg.g(name) if seg.grad is not None else None
+    def __init__(self, seg: Segment, name: Optional[str], at=None):
+        offset, shape = at if at is not None else seg.index[name]
+        n = math.prod(shape)
+        self.w, self.b, self.g = (None if flat is None else flat[offset:offset + n].view(shape)
+                                  for flat in (seg.fp32, seg.bf16, seg.grad))
+
+    @classmethod
+    def span(cls, seg: Segment, offset: int, shape) -> "_P":
+        """``shape`` elements at ``offset`` of the flat buffers: parameters laid out back to back and read as one (the
+        ViT's fused q|k|v)."""
+        return cls(seg, None, (offset, tuple(shape)))
 
 
 # ------------------------------------------------------------------------------------------ GPT-2 trunk
+@dataclass
+class DecodeState:
+    """K/V cache of one incremental decode (``GptTrunk.decode_cache``) and how far it is filled."""
+    kv: List[torch.Tensor]     # per layer: [R * smax, 3H] bf16, the layer's slice of ``kv_all``
+    kv_all: torch.Tensor       # [L, R * smax, 3H]: ONE allocation, so a beam reorder is one gather
+    att: torch.Tensor          # [R * smax, H] bf16 attention output rows, shared by the layers
+    cu: torch.Tensor           # [R + 1] int32: cu[r] = r * smax
+    R: int
+    smax: int
+    t: int = 0                 # position of the last step
+    lnf_done: bool = False     # the last step left ln_f(x) in ``gen.y`` (skinny path): the LM head's operand
+
+
 class GptTrunk:
     """GPT-2 blocks + ln_f on an f32 residual stream (HF GPT2Block, modeling_gpt2.py:246-310).
 
@@ -342,14 +388,11 @@ class GptTrunk:
         if save and S > ATTN_BWD_MAX_S:
             raise ValueError(f"training needs sequence length <= {ATTN_BWD_MAX_S} (attention backward keeps the query "
                              f"gradients of every 128-token block in registers); got {S}")
-        M = Bq * S
-        cu = rows = None
-        nseq = Bq
-        if pack is not None:   # the filler rows are one more (unmasked) sequence of the attention launch
-            M, cu, rows, mask, nseq = pack.Mp, pack.cu, pack.row_ids, pack.mask, pack.nseq
-        L = len(self.layers)
+        rw = _rows(pack, Bq, S)
+        M = rw.M
+        if pack is not None:   # its key mask has the rows of the filler: more (unmasked) sequences of the attention launch
+            mask = pack.mask
         sv = {"M": M, "Bq": Bq, "S": S, "mask": mask, "drop": drop, "pack": pack} if save else None
-        dsite = (lambda li, kind: drop(li, kind)) if drop is not None else (lambda li, kind: None)
         h = h0
         for li, P in enumerate(self.layers):
             k = f"l{li}." if save else ""
@@ -360,11 +403,11 @@ class GptTrunk:
             qkv = self._buf(k + "qkv", (M, 3 * H), BF16)
             hip.gemm(ln1, P["wqkv"].b, M, 3 * H, H, hip.NN, bias=P["bqkv"].w, out_bf16=qkv)
             att = self._buf(k + "att", (M, H), BF16)
-            lse = self._buf(k + "lse", (nseq, a.heads, S), F32)
-            hip.attention_fwd(qkv, mask, nseq, S, a.heads, True, att, lse, drop=dsite(li, KIND_ATTN), cu=cu)
+            lse = self._buf(k + "lse", (rw.nseq, a.heads, S), F32)
+            hip.attention_fwd(qkv, mask, rw.nseq, S, a.heads, True, att, lse, drop=_dsite(drop, li, KIND_ATTN), cu=rw.cu)
             hm = self._buf(k + "hm", (M, H), F32) if save else h
             hip.gemm(att, P["wo"].b, M, H, H, hip.NN, bias=P["bo"].w, residual=h, out_f32=hm,
-                     drop=dsite(li, KIND_RESID_ATTN), drop_rows=rows)
+                     drop=_dsite(drop, li, KIND_RESID_ATTN), drop_rows=rw.ids)
             ln2 = self._buf(k + "ln2", (M, H), BF16)
             m2 = self._buf(k + "m2", (M,), F32)
             r2 = self._buf(k + "r2", (M,), F32)
@@ -378,7 +421,7 @@ class GptTrunk:
                      bias=P["bfc"].w, out_bf16=act, aux_out=pre)
             hn = self._buf(f"l{li + 1}.hin", (M, H), F32) if save else hm
             hip.gemm(act, P["wpr"].b, M, H, I, hip.NN, bias=P["bpr"].w, residual=hm, out_f32=hn,
-                     drop=dsite(li, KIND_RESID_MLP), drop_rows=rows)
+                     drop=_dsite(drop, li, KIND_RESID_MLP), drop_rows=rw.ids)
             if save:
                 sv[li] = dict(hin=h, ln1=ln1, m1=m1, r1=r1, qkv=qkv, att=att, lse=lse, hm=hm, ln2=ln2, m2=m2, r2=r2,
                               act=act, pre=pre)
@@ -391,25 +434,20 @@ class GptTrunk:
     # -- incremental decoding (generation) ---------------------------------------------------------
     SKINNY_ROWS = 32   # up to this many sequences a decode step runs on pgca_gemm_skinny (faster than the tile GEMMs up to 32 rows: DESIGN 5)
 
-    def decode_cache(self, R: int, smax: int) -> dict:
+    def decode_cache(self, R: int, smax: int) -> DecodeState:
         """Per-layer K/V cache of an incremental decode over ``R`` sequences of at most ``smax`` positions: one resident
         ``[R * smax, 3H]`` bf16 buffer per layer in the SAME q|k|v row layout the attention kernel reads (row r*smax + t
         holds position t of sequence r), plus the shared attention-output rows and the offsets ``cu[r] = r * smax``."""
         a, H = self.arch, self.arch.hidden
         if smax > a.n_pos:
             raise ValueError(f"{smax} positions exceed GPT-2's {a.n_pos} learned positions")
-        L = len(self.layers)
-        kv_all = self._buf("gen.kv", (L, R * smax, 3 * H), BF16)     # ONE allocation: a beam reorder is one gather
-        kv = [kv_all[li] for li in range(L)]
+        kv_all = self._buf("gen.kv", (len(self.layers), R * smax, 3 * H), BF16)
         att = self._buf("gen.att", (R * smax, H), BF16)
-        cu = self.ws.bufs.get(self.tag + ".gen.cu")
-        if cu is None or cu.numel() != R + 1 or int(getattr(self, "_gen_smax", -1)) != smax:
-            cu = (torch.arange(R + 1, dtype=I32, device=self.ws.device) * smax).contiguous()
-            self.ws.bufs[self.tag + ".gen.cu"] = cu
-            self._gen_smax = smax
-        return dict(kv=kv, kv_all=kv_all, att=att, cu=cu, R=R, smax=smax)
+        cu = self.ws.cached(self.tag + ".gen.cu", (R, smax),
+                            lambda: (torch.arange(R + 1, dtype=I32, device=self.ws.device) * smax).contiguous())
+        return DecodeState(kv=list(kv_all), kv_all=kv_all, att=att, cu=cu, R=R, smax=smax)
 
-    def decode_step(self, x: torch.Tensor, st: dict, t: int) -> torch.Tensor:
+    def decode_step(self, x: torch.Tensor, st: DecodeState, t: int) -> torch.Tensor:
         """One position of an incremental forward: ``x`` [R, H] f32 is the input embedding (+ position) of position
         ``t`` of every sequence; keys / values of positions < t come from the cache ``st`` (HF ``use_cache``,
         modeling_gpt2.py:144-226 with ``layer_past``).  Updates ``x`` in place to the residual stream after the last
@@ -417,12 +455,12 @@ class GptTrunk:
         are rewritten with the values they already had): at caption lengths (<= 128: one key tile) that costs nothing
         next to the weight reads of the R-row GEMMs."""
         a, H, I = self.arch, self.arch.hidden, self.arch.inner
-        R, smax = st["R"], st["smax"]
+        R, smax = st.R, st.smax
         if not 0 <= t < smax:
             raise ValueError(f"position {t} outside the cache ({smax})")
         y = self._buf("gen.y", (R, H), BF16)
         act = self._buf("gen.act", (R, I), BF16)
-        att = st["att"]
+        att = st.att
         att_t = att.view(-1)[t * H:]
         L = len(self.layers)
         if R <= min(self.SKINNY_ROWS, hip.SKINNY_MAX_M) and I <= 8192 and 3 * H <= 8192:
@@ -433,10 +471,10 @@ class GptTrunk:
             P0 = self.layers[0]
             hip.layernorm_fwd(x, R, H, P0["ln1w"].w, P0["ln1b"].w, a.eps, y_bf16=y)
             for li, P in enumerate(self.layers):
-                kv = st["kv"][li]
+                kv = st.kv[li]
                 hip.gemm_skinny(y, P["wqkv"].b, R, 3 * H, H, sc, bias=P["bqkv"].w, out_bf16=kv.view(-1)[t * 3 * H:],
                                 ld_out_bf16=smax * 3 * H)
-                hip.attention_fwd(kv, None, R, t + 1, a.heads, True, att, None, cu=st["cu"])
+                hip.attention_fwd(kv, None, R, t + 1, a.heads, True, att, None, cu=st.cu)
                 hip.gemm_skinny(att_t, P["wo"].b, R, H, H, sc, lda=smax * H, bias=P["bo"].w, residual=x, out_f32=x,
                                 ln=(P["ln2w"].w, P["ln2b"].w, a.eps), ln_out=y)
                 hip.gemm_skinny(y, P["wfc"].b, R, I, H, sc, bias=P["bfc"].w, act=hip.EPI_GELU_NEW, out_bf16=act)
@@ -444,25 +482,24 @@ class GptTrunk:
                     (self.lnf_w.w, self.lnf_b.w)
                 hip.gemm_skinny(act, P["wpr"].b, R, H, I, sc, bias=P["bpr"].w, residual=x, out_f32=x,
                                 ln=(nxt[0], nxt[1], a.eps), ln_out=y)
-            st["lnf_done"] = True      # y holds ln_f(x): the LM head's operand
+            st.lnf_done = True      # y holds ln_f(x): the LM head's operand
             return x
-        st["lnf_done"] = False
+        st.lnf_done = False
         for li, P in enumerate(self.layers):
-            kv = st["kv"][li]
+            kv = st.kv[li]
             hip.layernorm_fwd(x, R, H, P["ln1w"].w, P["ln1b"].w, a.eps, y_bf16=y)
             hip.gemm(y, P["wqkv"].b, R, 3 * H, H, hip.NN, bias=P["bqkv"].w, out_bf16=kv.view(-1)[t * 3 * H:],
                      ld_out_bf16=smax * 3 * H)
-            hip.attention_fwd(kv, None, R, t + 1, a.heads, True, att, None, cu=st["cu"])
+            hip.attention_fwd(kv, None, R, t + 1, a.heads, True, att, None, cu=st.cu)
             hip.gemm(att_t, P["wo"].b, R, H, H, hip.NN, lda=smax * H, bias=P["bo"].w, residual=x, out_f32=x)
             hip.layernorm_fwd(x, R, H, P["ln2w"].w, P["ln2b"].w, a.eps, y_bf16=y)
             hip.gemm(y, P["wfc"].b, R, I, H, hip.NN, epilogue=hip.EPI_GELU_NEW, bias=P["bfc"].w, out_bf16=act)
             hip.gemm(act, P["wpr"].b, R, H, I, hip.NN, bias=P["bpr"].w, residual=x, out_f32=x)
         return x
 
-    def decode_reorder(self, st: dict, src: torch.Tensor) -> None:
+    def decode_reorder(self, st: DecodeState, src: torch.Tensor) -> None:
         """Beam search: sequence r continues from cached sequence ``src[r]`` (HF ``_reorder_cache``)."""
-        R, smax = st["R"], st["smax"]
-        v = st["kv_all"].view(len(self.layers), R, smax, -1)[:, :, :st.get("t", smax - 1) + 1]   # the filled positions
+        v = st.kv_all.view(len(self.layers), st.R, st.smax, -1)[:, :, :st.t + 1]   # the filled positions
         v.copy_(v.index_select(1, src))
 
     def top_drop(self):
@@ -483,14 +520,12 @@ class GptTrunk:
         assert sv is not None, "forward(save=True) must precede backward"
         a, H, I = self.arch, self.arch.hidden, self.arch.inner
         M, Bq, S = sv["M"], sv["Bq"], sv["S"]
-        pack: Optional[RowPack] = sv.get("pack")
-        cu, rows, nseq = (pack.cu, pack.row_ids, pack.nseq) if pack is not None else (None, None, Bq)
+        rw = _rows(sv["pack"], Bq, S)
         ws = self.ws
         nb = hip.layernorm_bwd_blocks(M)
         part4 = ws.get("ln_part", (4, nb, H), F32)   # planes: dgamma, dbeta, sum(add_to), sum(dx_out)
         part, partx = part4[:2], part4[2:]
-        drop = sv.get("drop")
-        dsite = (lambda li, kind: drop(li, kind)) if drop is not None else (lambda li, kind: None)
+        drop = sv["drop"]
         L = len(self.layers)
         main = torch.cuda.current_stream()
         side = None
@@ -529,8 +564,8 @@ class GptTrunk:
             g2 = self._buf("g_b" if (li & 1) else "g_a", (M, H), F32)
             g2_bf = self._buf("gbf_b" if (li & 1) else "gbf_a", (M, H), BF16)
             hip.layernorm_bwd(s["hm"], M, H, P["ln2w"].w, s["m2"], s["r2"], g2, dy_bf16=dln, add_to=g, dx_bf16=g2_bf,
-                              part=part, part_extra=partx, drop_add=dsite(li, KIND_RESID_MLP),
-                              drop_dx=dsite(li, KIND_RESID_ATTN), drop_rows=rows)
+                              part=part, part_extra=partx, drop_add=_dsite(drop, li, KIND_RESID_MLP),
+                              drop_dx=_dsite(drop, li, KIND_RESID_ATTN), drop_rows=rw.ids)
             # the same pass summed g (bias gradient of mlp.c_proj) and g2 (bias gradient of attn.c_proj)
             _ln_param_grads(part4, nb, H, P["ln2w"].g, P["ln2b"].g, P["bpr"].g, P["bo"].g)
             # ---- attention: hm = hin + c_proj(attn(c_attn(ln1(hin))))
@@ -538,8 +573,8 @@ class GptTrunk:
             hip.gemm(g2_bf, P["wo"].b, M, H, H, hip.NT, out_bf16=datt)
             wgrads.append((s["att"], g2_bf, H, H, M, P["wo"].g))
             dqkv = self._buf("dqkv" + par, (M, 3 * H), BF16)
-            hip.attention_bwd(s["qkv"], s["att"], datt, s["lse"], sv["mask"], nseq, S, a.heads, True, dqkv,
-                              drop=dsite(li, KIND_ATTN), cu=cu)
+            hip.attention_bwd(s["qkv"], s["att"], datt, s["lse"], sv["mask"], rw.nseq, S, a.heads, True, dqkv,
+                              drop=_dsite(drop, li, KIND_ATTN), cu=rw.cu)
             hip.gemm(dqkv, P["wqkv"].b, M, H, 3 * H, hip.NT, out_bf16=dln)
             wgrads.append((s["ln1"], dqkv, H, 3 * H, M, P["wqkv"].g))
             # one launch, whole K per tile: no split-K atomics (gemm256_group_tn_kernel)
@@ -559,7 +594,7 @@ class GptTrunk:
             settle(li + 1)   # that launch read its incoming g_bf from the buffer g3_bf is about to overwrite
             hip.layernorm_bwd(s["hin"], M, H, P["ln1w"].w, s["m1"], s["r1"], g3, dy_bf16=dln, add_to=g2,
                               dx_bf16=g3_bf, part=part,
-                              drop_dx=dsite(li - 1, KIND_RESID_MLP) if li > 0 else None, drop_rows=rows)
+                              drop_dx=_dsite(drop, li - 1, KIND_RESID_MLP) if li > 0 else None, drop_rows=rw.ids)
             _ln_param_grads(part, nb, H, P["ln1w"].g, P["ln1b"].g)
             g, g_bf = g3, g3_bf
             if side is None and self.grad_hook is not None:
@@ -638,21 +673,13 @@ class VisionTower:
         seg = store.seg_of(p + ".post_layernorm.weight")
         self.seg = seg
         self.trainable = seg.grad is not None
-        G = (lambda n: seg.g(n)) if self.trainable else (lambda n: None)
-        self._g = G
-        self._names = dict(cls=p + ".embeddings.class_embedding", pos=p + ".embeddings.position_embedding.weight",
-                           patch=p + ".embeddings.patch_embedding.weight")
-        self.cls = seg.w(self._names["cls"])
-        self.pos = seg.w(self._names["pos"])
-        self._wpatch_name = self._names["patch"]
+        self.cls, self.pos, self.wpatch, self.pre_w, self.pre_b, self.post_w, self.post_b = (_P(seg, p + n) for n in (
+            ".embeddings.class_embedding", ".embeddings.position_embedding.weight", ".embeddings.patch_embedding.weight",
+            ".pre_layrnorm.weight", ".pre_layrnorm.bias", ".post_layernorm.weight", ".post_layernorm.bias"))
         # K of the patch-embedding GEMM: 3*P*P, padded with zero columns to the GEMM's 64-deep tile when it is not a
         # multiple of 8 (ViT-L/14: 588 -> 640); the padded bf16 weight is a private copy refreshed when the mirror changes
         self.patch_k = arch.patch_dim if arch.patch_dim % 8 == 0 else (arch.patch_dim + 63) // 64 * 64
         self._wpatch_pad, self._wpatch_ver = None, -1
-        self.pre = (seg.w(p + ".pre_layrnorm.weight"), seg.w(p + ".pre_layrnorm.bias"))
-        self.post = (seg.w(p + ".post_layernorm.weight"), seg.w(p + ".post_layernorm.bias"))
-        self.pre_g = (G(p + ".pre_layrnorm.weight"), G(p + ".pre_layrnorm.bias"))
-        self.post_g = (G(p + ".post_layernorm.weight"), G(p + ".post_layernorm.bias"))
         H = arch.hidden
         self.layers = []
         for i in range(arch.layers):
@@ -661,27 +688,18 @@ class VisionTower:
             bq_off = seg.index[q + ".self_attn.q_proj.bias"][0]
             assert seg.index[q + ".self_attn.v_proj.weight"][0] == wq_off + 2 * H * H, "q,k,v must be contiguous"
             assert seg.index[q + ".self_attn.v_proj.bias"][0] == bq_off + 2 * H
-            L = dict(
-                wqkv=seg.bf16[wq_off:wq_off + 3 * H * H].view(3 * H, H), bqkv=seg.fp32[bq_off:bq_off + 3 * H],
-                wo=seg.wb(q + ".self_attn.out_proj.weight"), bo=seg.w(q + ".self_attn.out_proj.bias"),
-                ln1=(seg.w(q + ".layer_norm1.weight"), seg.w(q + ".layer_norm1.bias")),
-                ln2=(seg.w(q + ".layer_norm2.weight"), seg.w(q + ".layer_norm2.bias")),
-                w1=seg.wb(q + ".mlp.fc1.weight"), b1=seg.w(q + ".mlp.fc1.bias"),
-                w2=seg.wb(q + ".mlp.fc2.weight"), b2=seg.w(q + ".mlp.fc2.bias"))
-            if self.trainable:
-                L.update(
-                    g_wqkv=seg.grad[wq_off:wq_off + 3 * H * H].view(3 * H, H), g_bqkv=seg.grad[bq_off:bq_off + 3 * H],
-                    g_wo=G(q + ".self_attn.out_proj.weight"), g_bo=G(q + ".self_attn.out_proj.bias"),
-                    g_ln1=(G(q + ".layer_norm1.weight"), G(q + ".layer_norm1.bias")),
-                    g_ln2=(G(q + ".layer_norm2.weight"), G(q + ".layer_norm2.bias")),
-                    g_w1=G(q + ".mlp.fc1.weight"), g_b1=G(q + ".mlp.fc1.bias"),
-                    g_w2=G(q + ".mlp.fc2.weight"), g_b2=G(q + ".mlp.fc2.bias"))
+            L = {k: _P(seg, q + n) for k, n in (
+                ("wo", ".self_attn.out_proj.weight"), ("bo", ".self_attn.out_proj.bias"),
+                ("ln1w", ".layer_norm1.weight"), ("ln1b", ".layer_norm1.bias"),
+                ("ln2w", ".layer_norm2.weight"), ("ln2b", ".layer_norm2.bias"),
+                ("w1", ".mlp.fc1.weight"), ("b1", ".mlp.fc1.bias"), ("w2", ".mlp.fc2.weight"), ("b2", ".mlp.fc2.bias"))}
+            L["wqkv"], L["bqkv"] = _P.span(seg, wq_off, (3 * H, H)), _P.span(seg, bq_off, (3 * H,))
             self.layers.append(L)
         self.saved: Optional[dict] = None
 
     def _patch_weight(self) -> torch.Tensor:
         """[H, patch_k] bf16 view of the conv weight (zero-padded copy when 3*P*P is not a multiple of 8)."""
-        w = self.seg.wb(self._wpatch_name).view(self.arch.hidden, self.arch.patch_dim)
+        w = self.wpatch.b.view(self.arch.hidden, self.arch.patch_dim)
         if self.patch_k == self.arch.patch_dim:
             return w
         if self._wpatch_pad is None or self._wpatch_ver != self.seg.bf16_version:
@@ -707,58 +725,45 @@ class VisionTower:
         pe = ws.get("vit.pe", (B * G * G, H), F32)
         hip.gemm(cols, self._patch_weight(), B * G * G, H, Kp, hip.NT, out_f32=pe)
         x0 = ws.get("vit.x0", (M, H), F32)
-        hip.vit_assemble(pe, self.cls, self.pos, B, T, H, x0)
+        hip.vit_assemble(pe, self.cls.w, self.pos.w, B, T, H, x0)
         x = ws.get("vit.x", (M, H), F32)
-        sv = None
-        if save:
-            sv = dict(B=B, M=M, cols=cols, x0=x0, m0=ws.get("vit.m0", (M,), F32), r0=ws.get("vit.r0", (M,), F32))
-            hip.layernorm_fwd(x0, M, H, self.pre[0], self.pre[1], a.eps, y_f32=x, mean=sv["m0"], rstd=sv["r0"])
-        else:
-            hip.layernorm_fwd(x0, M, H, self.pre[0], self.pre[1], a.eps, y_f32=x)
-        for li, Lw in enumerate(self.layers):
+        # ``save`` only chooses where a launch writes: without it the stream is updated in place, one set of buffers serves
+        # every layer and no statistics are kept
+        m0, r0 = (ws.get(n, (M,), F32) if save else None for n in ("vit.m0", "vit.r0"))
+        hip.layernorm_fwd(x0, M, H, self.pre_w.w, self.pre_b.w, a.eps, y_f32=x, mean=m0, rstd=r0)
+        sv = dict(B=B, M=M, cols=cols, x0=x0, m0=m0, r0=r0) if save else None
+        for li, P in enumerate(self.layers):
             k = f"vit.l{li}." if save else "vit."
             y = ws.get(k + "y", (M, H), BF16)
             qkv = ws.get(k + "qkv", (M, 3 * H), BF16)
             att = ws.get(k + "att", (M, H), BF16)
             act = ws.get(k + "act", (M, a.mlp), BF16)
-            if not save:   # in place on the residual stream, nothing kept
-                hip.layernorm_fwd(x, M, H, Lw["ln1"][0], Lw["ln1"][1], a.eps, y_bf16=y)
-                hip.gemm(y, Lw["wqkv"], M, 3 * H, H, hip.NT, bias=Lw["bqkv"], out_bf16=qkv)
-                hip.attention_fwd(qkv, None, B, T, a.heads, False, att, None)
-                hip.gemm(att, Lw["wo"], M, H, H, hip.NT, bias=Lw["bo"], residual=x, out_f32=x)
-                hip.layernorm_fwd(x, M, H, Lw["ln2"][0], Lw["ln2"][1], a.eps, y_bf16=y)
-                hip.gemm(y, Lw["w1"], M, a.mlp, H, hip.NT, epilogue=hip.EPI_QUICK_GELU, bias=Lw["b1"], out_bf16=act)
-                hip.gemm(act, Lw["w2"], M, H, a.mlp, hip.NT, bias=Lw["b2"], residual=x, out_f32=x)
-                continue
-            s = dict(xin=x, y1=y, qkv=qkv, att=att, act=act,
-                     m1=ws.get(k + "m1", (M,), F32), r1=ws.get(k + "r1", (M,), F32),
-                     m2=ws.get(k + "m2", (M,), F32), r2=ws.get(k + "r2", (M,), F32),
-                     lse=ws.get(k + "lse", (B, a.heads, T), F32), xm=ws.get(k + "xm", (M, H), F32),
-                     y2=ws.get(k + "y2", (M, H), BF16), pre=ws.get(k + "pre", (M, a.mlp), BF16))
-            hip.layernorm_fwd(x, M, H, Lw["ln1"][0], Lw["ln1"][1], a.eps, y_bf16=y, mean=s["m1"], rstd=s["r1"])
-            hip.gemm(y, Lw["wqkv"], M, 3 * H, H, hip.NT, bias=Lw["bqkv"], out_bf16=qkv)
-            hip.attention_fwd(qkv, None, B, T, a.heads, False, att, s["lse"])
-            hip.gemm(att, Lw["wo"], M, H, H, hip.NT, bias=Lw["bo"], residual=x, out_f32=s["xm"])
-            hip.layernorm_fwd(s["xm"], M, H, Lw["ln2"][0], Lw["ln2"][1], a.eps, y_bf16=s["y2"], mean=s["m2"], rstd=s["r2"])
-            hip.gemm(s["y2"], Lw["w1"], M, a.mlp, H, hip.NT, epilogue=hip.EPI_QUICK_GELU, bias=Lw["b1"], out_bf16=act,
-                     aux_out=s["pre"])
-            xn = ws.get(f"vit.l{li + 1}.xin", (M, H), F32)
-            hip.gemm(act, Lw["w2"], M, H, a.mlp, hip.NT, bias=Lw["b2"], residual=s["xm"], out_f32=xn)
-            sv[li] = s
+            m1, r1, m2, r2 = (ws.get(k + n, (M,), F32) if save else None for n in ("m1", "r1", "m2", "r2"))
+            lse = ws.get(k + "lse", (B, a.heads, T), F32) if save else None
+            hip.layernorm_fwd(x, M, H, P["ln1w"].w, P["ln1b"].w, a.eps, y_bf16=y, mean=m1, rstd=r1)
+            hip.gemm(y, P["wqkv"].b, M, 3 * H, H, hip.NT, bias=P["bqkv"].w, out_bf16=qkv)
+            hip.attention_fwd(qkv, None, B, T, a.heads, False, att, lse)
+            xm = ws.get(k + "xm", (M, H), F32) if save else x
+            hip.gemm(att, P["wo"].b, M, H, H, hip.NT, bias=P["bo"].w, residual=x, out_f32=xm)
+            y2 = ws.get(k + "y2", (M, H), BF16) if save else y
+            hip.layernorm_fwd(xm, M, H, P["ln2w"].w, P["ln2b"].w, a.eps, y_bf16=y2, mean=m2, rstd=r2)
+            pre = ws.get(k + "pre", (M, a.mlp), BF16) if save else None
+            hip.gemm(y2, P["w1"].b, M, a.mlp, H, hip.NT, epilogue=hip.EPI_QUICK_GELU, bias=P["b1"].w, out_bf16=act,
+                     aux_out=pre)
+            xn = ws.get(f"vit.l{li + 1}.xin", (M, H), F32) if save else x
+            hip.gemm(act, P["w2"].b, M, H, a.mlp, hip.NT, bias=P["b2"].w, residual=xm, out_f32=xn)
+            if save:
+                sv[li] = dict(xin=x, y1=y, qkv=qkv, att=att, act=act, m1=m1, r1=r1, m2=m2, r2=r2, lse=lse, xm=xm, y2=y2,
+                              pre=pre)
             x = xn
-        cls_rows = ws.bufs.get("vit.clsrows")
-        if cls_rows is None or cls_rows.numel() != B:
-            cls_rows = (torch.arange(B, dtype=I32, device=ws.device) * T).contiguous()
-            ws.bufs["vit.clsrows"] = cls_rows
+        cls_rows = ws.cached("vit.clsrows", (B, T), lambda: (torch.arange(B, dtype=I32, device=ws.device) * T).contiguous())
         pooled = ws.get("vit.pooled", (B, H), F32)
         pooled_bf = ws.get("vit.pooledbf", (B, H), BF16)
+        mp, rp = (ws.get(n, (B,), F32) if save else None for n in ("vit.mp", "vit.rp"))
+        hip.layernorm_fwd(x, B, H, self.post_w.w, self.post_b.w, a.eps, row_map=cls_rows, y_f32=pooled, y_bf16=pooled_bf,
+                          mean=mp, rstd=rp)
         if save:
-            sv.update(xL=x, cls_rows=cls_rows, mp=ws.get("vit.mp", (B,), F32), rp=ws.get("vit.rp", (B,), F32))
-            hip.layernorm_fwd(x, B, H, self.post[0], self.post[1], a.eps, row_map=cls_rows, y_f32=pooled,
-                              y_bf16=pooled_bf, mean=sv["mp"], rstd=sv["rp"])
-        else:
-            hip.layernorm_fwd(x, B, H, self.post[0], self.post[1], a.eps, row_map=cls_rows, y_f32=pooled,
-                              y_bf16=pooled_bf)
+            sv.update(xL=x, cls_rows=cls_rows, mp=mp, rp=rp)
         self.saved = sv
         return x.view(B, T, H), pooled, pooled_bf
 
@@ -778,9 +783,9 @@ class VisionTower:
         g.zero_()
         nbp = hip.layernorm_bwd_blocks(B)
         partp = ws.get("vit.ln_part_cls", (2, nbp, H), F32)
-        hip.layernorm_bwd(sv["xL"], B, H, self.post[0], sv["mp"], sv["rp"], g, dy_f32=dpooled, row_map=sv["cls_rows"],
+        hip.layernorm_bwd(sv["xL"], B, H, self.post_w.w, sv["mp"], sv["rp"], g, dy_f32=dpooled, row_map=sv["cls_rows"],
                           part=partp)
-        _ln_param_grads(partp, nbp, H, self.post_g[0], self.post_g[1])
+        _ln_param_grads(partp, nbp, H, self.post_w.g, self.post_b.g)
         g_bf = ws.get("vit.gbf_a", (M, H), BF16)
         hip.cast_bf16(g, g_bf, M * H)
         dpre = ws.get("vit.dpre", (M, I), BF16)
@@ -788,39 +793,39 @@ class VisionTower:
         datt = ws.get("vit.datt", (M, H), BF16)
         dqkv = ws.get("vit.dqkv", (M, 3 * H), BF16)
         for li in range(len(self.layers) - 1, -1, -1):
-            Lw, s = self.layers[li], sv[li]
+            P, s = self.layers[li], sv[li]
             # ---- MLP: x_out = xm + fc2(quick_gelu(fc1(ln2(xm))))
-            hip.gemm(g_bf, Lw["w2"], M, I, H, hip.NN, epilogue=hip.EPI_DQUICK_GELU, aux_in=s["pre"], out_bf16=dpre)
-            hip.gemm(g_bf, s["act"], H, I, M, hip.TN, lda=H, ldb=I, out_f32=Lw["g_w2"], accumulate=True)
-            _bias_grad(ws, M, H, H, Lw["g_b2"], x_f32=g)
-            hip.gemm(dpre, Lw["w1"], M, H, I, hip.NN, out_bf16=dln)
-            hip.gemm(dpre, s["y2"], I, H, M, hip.TN, lda=I, ldb=H, out_f32=Lw["g_w1"], accumulate=True)
-            _bias_grad(ws, M, I, I, Lw["g_b1"], x_bf16=dpre)
+            hip.gemm(g_bf, P["w2"].b, M, I, H, hip.NN, epilogue=hip.EPI_DQUICK_GELU, aux_in=s["pre"], out_bf16=dpre)
+            hip.gemm(g_bf, s["act"], H, I, M, hip.TN, lda=H, ldb=I, out_f32=P["w2"].g, accumulate=True)
+            _bias_grad(ws, M, H, H, P["b2"].g, x_f32=g)
+            hip.gemm(dpre, P["w1"].b, M, H, I, hip.NN, out_bf16=dln)
+            hip.gemm(dpre, s["y2"], I, H, M, hip.TN, lda=I, ldb=H, out_f32=P["w1"].g, accumulate=True)
+            _bias_grad(ws, M, I, I, P["b1"].g, x_bf16=dpre)
             g2 = ws.get("vit.g_b", (M, H), F32)
             g2_bf = ws.get("vit.gbf_b", (M, H), BF16)
-            hip.layernorm_bwd(s["xm"], M, H, Lw["ln2"][0], s["m2"], s["r2"], g2, dy_bf16=dln, add_to=g, dx_bf16=g2_bf,
+            hip.layernorm_bwd(s["xm"], M, H, P["ln2w"].w, s["m2"], s["r2"], g2, dy_bf16=dln, add_to=g, dx_bf16=g2_bf,
                               part=part)
-            _ln_param_grads(part, nb, H, Lw["g_ln2"][0], Lw["g_ln2"][1])
+            _ln_param_grads(part, nb, H, P["ln2w"].g, P["ln2b"].g)
             # ---- attention: xm = xin + out_proj(attn(qkv(ln1(xin))))
-            hip.gemm(g2_bf, Lw["wo"], M, H, H, hip.NN, out_bf16=datt)
-            hip.gemm(g2_bf, s["att"], H, H, M, hip.TN, lda=H, ldb=H, out_f32=Lw["g_wo"], accumulate=True)
-            _bias_grad(ws, M, H, H, Lw["g_bo"], x_f32=g2)
+            hip.gemm(g2_bf, P["wo"].b, M, H, H, hip.NN, out_bf16=datt)
+            hip.gemm(g2_bf, s["att"], H, H, M, hip.TN, lda=H, ldb=H, out_f32=P["wo"].g, accumulate=True)
+            _bias_grad(ws, M, H, H, P["bo"].g, x_f32=g2)
             hip.attention_bwd(s["qkv"], s["att"], datt, s["lse"], None, B, T, a.heads, False, dqkv)
-            hip.gemm(dqkv, Lw["wqkv"], M, H, 3 * H, hip.NN, out_bf16=dln)
-            hip.gemm(dqkv, s["y1"], 3 * H, H, M, hip.TN, lda=3 * H, ldb=H, out_f32=Lw["g_wqkv"], accumulate=True)
-            _bias_grad(ws, M, 3 * H, 3 * H, Lw["g_bqkv"], x_bf16=dqkv)
-            hip.layernorm_bwd(s["xin"], M, H, Lw["ln1"][0], s["m1"], s["r1"], g, dy_bf16=dln, add_to=g2, dx_bf16=g_bf,
+            hip.gemm(dqkv, P["wqkv"].b, M, H, 3 * H, hip.NN, out_bf16=dln)
+            hip.gemm(dqkv, s["y1"], 3 * H, H, M, hip.TN, lda=3 * H, ldb=H, out_f32=P["wqkv"].g, accumulate=True)
+            _bias_grad(ws, M, 3 * H, 3 * H, P["bqkv"].g, x_bf16=dqkv)
+            hip.layernorm_bwd(s["xin"], M, H, P["ln1w"].w, s["m1"], s["r1"], g, dy_bf16=dln, add_to=g2, dx_bf16=g_bf,
                               part=part)
-            _ln_param_grads(part, nb, H, Lw["g_ln1"][0], Lw["g_ln1"][1])
+            _ln_param_grads(part, nb, H, P["ln1w"].g, P["ln1b"].g)
         # ---- pre_layrnorm, embeddings
         dx0 = ws.get("vit.g_b", (M, H), F32)
-        hip.layernorm_bwd(sv["x0"], M, H, self.pre[0], sv["m0"], sv["r0"], dx0, dy_f32=g, part=part)
-        _ln_param_grads(part, nb, H, self.pre_g[0], self.pre_g[1])
+        hip.layernorm_bwd(sv["x0"], M, H, self.pre_w.w, sv["m0"], sv["r0"], dx0, dy_f32=g, part=part)
+        _ln_param_grads(part, nb, H, self.pre_w.g, self.pre_b.g)
         Np, D, Kp = B * (T - 1), a.patch_dim, self.patch_k
         dpe = ws.get("vit.dpe", (Np, H), BF16)
-        hip.vit_assemble_bwd(dx0, B, T, H, dpe, self._g(self._names["cls"]), self._g(self._names["pos"]))
+        hip.vit_assemble_bwd(dx0, B, T, H, dpe, self.cls.g, self.pos.g)
         # conv weight [H, 3, P, P] == [H, D]: dW = dpe^t cols (the zero pad columns of ``cols`` are not read)
-        hip.gemm(dpe, sv["cols"], H, D, Np, hip.TN, lda=H, ldb=Kp, out_f32=self._g(self._names["patch"]).view(H, D),
+        hip.gemm(dpe, sv["cols"], H, D, Np, hip.TN, lda=H, ldb=Kp, out_f32=self.wpatch.g.view(H, D),
                  accumulate=True)
 
 
@@ -855,6 +860,8 @@ class CaptionDecoderEngine:
         self.ow, self.ob = _P(seg, p + ".cross_attention.out_proj.weight"), _P(seg, p + ".cross_attention.out_proj.bias")
         self.anw, self.anb = _P(seg, p + ".attention_norm.weight"), _P(seg, p + ".attention_norm.bias")
         self.saved = None
+        self._dec: Optional[DecodeState] = None   # the decode in flight (decode_begin)
+        self._graphs: dict = {}                   # captured decode steps (decode_advance)
 
     def _buf(self, name, shape, dtype, zero=False):
         return self.ws.get(f"{self.tag}.{name}", shape, dtype, zero)
@@ -873,7 +880,7 @@ class CaptionDecoderEngine:
         pv = self._buf("pv", (Bq, H), BF16)
         pv_raw = self._buf("pv_raw", (Bq, H), BF16) if drop is not None else None
         hip.gemm(emb_bf, self.vp_w.b, Bq, H, Pd, hip.NT, epilogue=hip.EPI_TANH, bias=self.vp_b.w, out_bf16=pv,
-                 aux_out=pv_raw, drop=drop(0, KIND_VPROJ) if drop is not None else None)
+                 aux_out=pv_raw, drop=_dsite(drop, 0, KIND_VPROJ))
         vv = self._buf("vv", (Bq, H), BF16)
         hip.gemm(pv, self.inw.b[2 * H:], Bq, H, H, hip.NT, bias=self.inb.w[2 * H:], out_bf16=vv)
         if drop is None:
@@ -894,18 +901,18 @@ class CaptionDecoderEngine:
         pack = sb.pack if packed else None
         if packed and pack is None:
             raise ValueError("packed=True needs a SeqBatch prepared with pack=True")
-        M = pack.Mp if pack is not None else Bq * S
-        pk = dict(row_ids=pack.row_ids, n_rows=M) if pack is not None else {}
+        rw = _rows(pack, Bq, S)
+        M = rw.M
         pf = self._prefix(emb, Bq, drop)
         h0 = self._buf("h0", (M, H), F32)
         m0, r0 = self._buf("m0", (M,), F32), self._buf("r0", (M,), F32)
         if drop is None:
             hip.embed_fwd(sb.ids, Bq, S, H, self.wte.w, self.wpe.w, h0, attended=pf["att"], gamma=self.anw.w,
-                          beta=self.anb.w, eps=1e-5, mean=m0, rstd=r0, **pk)
+                          beta=self.anb.w, eps=1e-5, mean=m0, rstd=r0, **rw.embed)
         else:
             hip.embed_fwd(sb.ids, Bq, S, H, self.wte.w, self.wpe.w, h0, attended=self.ob.w, att_stride=0,
                           gamma=self.anw.w, beta=self.anb.w, eps=1e-5, mean=m0, rstd=r0, U=pf["U"], xheads=XH,
-                          drop_x=drop(0, KIND_XATTN), drop_e=drop(0, KIND_EMBD), **pk)
+                          drop_x=drop(0, KIND_XATTN), drop_e=drop(0, KIND_EMBD), **rw.embed)
         hL = self.trunk.forward(h0, sb.mask, Bq, S, save, drop, pack=pack)
         if save:
             self.saved = dict(sb=sb, m0=m0, r0=r0, hL=hL, drop=drop, pack=pack, **pf)
@@ -999,7 +1006,6 @@ class CaptionDecoderEngine:
         first token [R, V].  ``max_positions`` = 1 + the most tokens that will be fed back."""
         R = pv.shape[0]
         self._dec = self.trunk.decode_cache(R, int(max_positions))
-        self._dec["t"] = 0
         x = self._buf("gen.x", (R, self.arch.gpt.hidden), F32)
         torch.add(pv, self.wpe.w[0], out=x)
         return self._decode_logits(x)
@@ -1012,7 +1018,7 @@ class CaptionDecoderEngine:
 
     def _advance_eager(self, tok: torch.Tensor, t: int) -> torch.Tensor:
         st = self._dec
-        x = self._buf("gen.x", (st["R"], self.arch.gpt.hidden), F32)
+        x = self._buf("gen.x", (st.R, self.arch.gpt.hidden), F32)
         torch.index_select(self.wte.w, 0, tok, out=x)
         x.add_(self.wpe.w[t])
         return self._decode_logits(x)
@@ -1020,20 +1026,20 @@ class CaptionDecoderEngine:
     def decode_advance(self, tokens: torch.Tensor) -> torch.Tensor:
         """Feed the tokens chosen for the current position ([R] int64); returns the next token's logits [R, V]."""
         st = self._dec
-        st["t"] += 1
-        t = st["t"]
+        st.t += 1
+        t = st.t
         if not (self.use_graphs and tokens.is_cuda):
             return self._advance_eager(tokens, t)
-        tok_in = self._buf("gen.tok_in", (st["R"],), I64)
+        tok_in = self._buf("gen.tok_in", (st.R,), I64)
         tok_in.copy_(tokens)
         # graphs hold raw pointers: they are only valid while every buffer they touch is the allocation they captured
-        stamp = (st["kv"][0].data_ptr(), st["kv"][-1].data_ptr(), st["att"].data_ptr(), tok_in.data_ptr(),
+        stamp = (st.kv[0].data_ptr(), st.kv[-1].data_ptr(), st.att.data_ptr(), tok_in.data_ptr(),
                  self.seg.bf16.data_ptr())
-        cache = self.__dict__.setdefault("_graphs", {})
+        cache = self._graphs
         if cache.get("stamp") != stamp:
             cache.clear()
             cache["stamp"] = stamp
-        key = (st["R"], st["smax"], t)
+        key = (st.R, st.smax, t)
         g = cache.get(key)
         if g is not None:
             g[0].replay()
@@ -1054,9 +1060,9 @@ class CaptionDecoderEngine:
 
     def _decode_logits(self, x: torch.Tensor) -> torch.Tensor:
         a, st = self.arch.gpt, self._dec
-        R, H = st["R"], a.hidden
-        self.trunk.decode_step(x, st, st["t"])
-        if st.get("lnf_done"):           # the last product's finish pass already ran ln_f
+        R, H = st.R, a.hidden
+        self.trunk.decode_step(x, st, st.t)
+        if st.lnf_done:                  # the last product's finish pass already ran ln_f
             hf = self.trunk._buf("gen.y", (R, H), BF16)
         else:
             hf = self._buf("gen.hf", (R, H), BF16)
@@ -1073,9 +1079,9 @@ class CaptionDecoderEngine:
         sb: SeqBatch = s["sb"]
         a = self.arch.gpt
         H, Pd, Bq, S, Mc = a.hidden, self.arch.proj_dim, sb.Bq, sb.S, sb.n_rows
-        pack: Optional[RowPack] = s.get("pack")
-        M = pack.Mp if pack is not None else Bq * S
-        cu, rows = (pack.cu, pack.row_ids) if pack is not None else (None, None)
+        pack: Optional[RowPack] = s["pack"]
+        rw = _rows(pack, Bq, S)
+        M = rw.M
         ws = self.ws
         rs = self._buf("row_scale", (Mc,), F32)
         # d tok_lp / d logits = onehot - softmax; the DLOGITS epilogue computes the cross-entropy form
@@ -1100,7 +1106,7 @@ class CaptionDecoderEngine:
         part = ws.get("ln_part_f", (2, nb, H), F32)
         hip.layernorm_bwd(s["hL"], Mc, H, self.trunk.lnf_w.w, s["mf"], s["rf"], g, dy_f32=dhf,
                           row_map=sb.row_map_packed if pack is not None else sb.row_map, dx_bf16=g_bf, part=part,
-                          drop_dx=self.trunk.top_drop(), drop_rows=rows)
+                          drop_dx=self.trunk.top_drop(), drop_rows=rw.ids)
         _ln_param_grads(part, nb, H, self.trunk.lnf_w.g, self.trunk.lnf_b.g)
         g0 = self.trunk.backward(g, g_bf)
         # embedding + attention_norm + 1-key cross-attention
@@ -1113,7 +1119,7 @@ class CaptionDecoderEngine:
         dvv = self._buf("dvv", (Bq, H), BF16)
         if drop is None:
             hip.embed_bwd(g0, sb.ids, sb.mask, Bq, S, H, self.wte.g, self.wpe.g, wte=self.wte.w, attended=s["att"],
-                          gamma=self.anw.w, mean=s["m0"], rstd=s["r0"], dattended=datt, part=parte, cu=cu)
+                          gamma=self.anw.w, mean=s["m0"], rstd=s["r0"], dattended=datt, part=parte, cu=rw.cu)
             _ln_param_grads(parte, nbe, H, self.anw.g, self.anb.g)
             datt_bf = self._buf("datt_bf", (Bq, H), BF16)
             hip.cast_bf16(datt, datt_bf, Bq * H)
@@ -1125,7 +1131,7 @@ class CaptionDecoderEngine:
             dU = self._buf("dU", (Bq, XH, H), F32, zero=True)
             hip.embed_bwd(g0, sb.ids, sb.mask, Bq, S, H, self.wte.g, self.wpe.g, wte=self.wte.w, attended=self.ob.w,
                           att_stride=0, gamma=self.anw.w, mean=s["m0"], rstd=s["r0"], dattended=datt, part=parte,
-                          U=s["U"], dU=dU, xheads=XH, drop_x=drop(0, KIND_XATTN), drop_e=drop(0, KIND_EMBD), cu=cu)
+                          U=s["U"], dU=dU, xheads=XH, drop_x=drop(0, KIND_XATTN), drop_e=drop(0, KIND_EMBD), cu=rw.cu)
             _ln_param_grads(parte, nbe, H, self.anw.g, self.anb.g)
             _bias_grad(ws, Bq, H, H, self.ob.g, x_f32=datt)        # d b_o = sum over rows of d e
             dU_bf = self._buf("dU_bf", (Bq, XH, H), BF16)
@@ -1140,7 +1146,7 @@ class CaptionDecoderEngine:
         _bias_grad(ws, Bq, H, H, self.inb.g[2 * H:], x_bf16=dvv)
         dpv = self._buf("dpv", (Bq, H), BF16)
         hip.gemm(dvv, self.inw.b[2 * H:], Bq, H, H, hip.NN, epilogue=hip.EPI_DTANH, aux_in=s["pv_raw"], out_bf16=dpv,
-                 drop=drop(0, KIND_VPROJ) if drop is not None else None)
+                 drop=_dsite(drop, 0, KIND_VPROJ))
         # pv = tanh(emb W_vp^t + b_vp)
         hip.gemm(dpv, s["emb_bf"], H, Pd, Bq, hip.TN, lda=H, ldb=Pd, out_f32=self.vp_w.g, accumulate=True)
         _bias_grad(ws, Bq, H, H, self.vp_b.g, x_bf16=dpv)
@@ -1174,18 +1180,16 @@ class TextTowerEngine:
         a = self.arch.gpt
         B, S = ids.shape
         H = a.hidden
-        M = pack.Mp if pack is not None else B * S
-        cu = pack.cu if pack is not None else None
-        pk = dict(row_ids=pack.row_ids, n_rows=M) if pack is not None else {}
+        rw = _rows(pack, B, S)
+        M = rw.M
         h0 = self._buf("h0", (M, H), F32)
-        hip.embed_fwd(ids, B, S, H, self.wte.w, self.wpe.w, h0, drop_e=drop(0, KIND_EMBD) if drop is not None else None,
-                      **pk)
+        hip.embed_fwd(ids, B, S, H, self.wte.w, self.wpe.w, h0, drop_e=_dsite(drop, 0, KIND_EMBD), **rw.embed)
         hL = self.trunk.forward(h0, mask, B, S, save and self.seg.grad is not None, drop, pack=pack)
         feats = self._buf("feats", (M, H), F32)
         mf, rf = self._buf("mf", (M,), F32), self._buf("rf", (M,), F32)
         hip.layernorm_fwd(hL, M, H, self.trunk.lnf_w.w, self.trunk.lnf_b.w, a.eps, y_f32=feats, mean=mf, rstd=rf)
         pooled = self._buf("pooled", (B, H), F32)
-        hip.masked_mean_fwd(feats, mask, B, S, H, pooled, cu=cu)
+        hip.masked_mean_fwd(feats, mask, B, S, H, pooled, cu=rw.cu)
         pooled_bf = self._buf("pooled_bf", (B, H), BF16)
         hip.cast_bf16(pooled, pooled_bf, B * H)
         emb = self.head.forward(pooled_bf, B, save, head_drop)
@@ -1196,15 +1200,15 @@ class TextTowerEngine:
     def backward(self, demb: torch.Tensor) -> None:
         s, a, ws = self.saved, self.arch.gpt, self.ws
         B, S, H = s["B"], s["S"], a.hidden
-        pack: Optional[RowPack] = s.get("pack")
-        M = pack.Mp if pack is not None else B * S
-        cu, rows = (pack.cu, pack.row_ids) if pack is not None else (None, None)
+        pack: Optional[RowPack] = s["pack"]
+        rw = _rows(pack, B, S)
+        M = rw.M
         if self.seg.grad is None:      # freeze_text_backbone=True (reference model.py:354-368): only the head trains
             self.head.backward(demb, need_dx=False)
             return
         dpooled = self.head.backward(demb, need_dx=True)
         dfeats = self._buf("dfeats", (M, H), F32)
-        hip.masked_mean_bwd(dpooled, s["mask"], B, S, H, dfeats, cu=cu)
+        hip.masked_mean_bwd(dpooled, s["mask"], B, S, H, dfeats, cu=rw.cu)
         if pack is not None and pack.Mp > pack.n:
             dfeats[pack.n:].zero_()    # filler rows: zero gradient
         g = self.trunk._buf("g_top", (M, H), F32)
@@ -1212,12 +1216,11 @@ class TextTowerEngine:
         nb = hip.layernorm_bwd_blocks(M)
         part = ws.get("ln_part_f", (2, nb, H), F32)
         hip.layernorm_bwd(s["hL"], M, H, self.trunk.lnf_w.w, s["mf"], s["rf"], g, dy_f32=dfeats, dx_bf16=g_bf, part=part,
-                          drop_dx=self.trunk.top_drop(), drop_rows=rows)
+                          drop_dx=self.trunk.top_drop(), drop_rows=rw.ids)
         _ln_param_grads(part, nb, H, self.trunk.lnf_w.g, self.trunk.lnf_b.g)
         g0 = self.trunk.backward(g, g_bf)
-        drop = s["drop"]
-        hip.embed_bwd(g0, s["ids"], s["mask"], B, S, H, self.wte.g, self.wpe.g,
-                      drop_e=drop(0, KIND_EMBD) if drop is not None else None, cu=cu)
+        hip.embed_bwd(g0, s["ids"], s["mask"], B, S, H, self.wte.g, self.wpe.g, drop_e=_dsite(s["drop"], 0, KIND_EMBD),
+                      cu=rw.cu)
 
 
 # ------------------------------------------------------------------------------------------ NT-Xent (Stage 1 loss)
@@ -1238,7 +1241,7 @@ class NTXentEngine:
         if proj_dim % 8:
             raise ValueError("projection_dim must be a multiple of 8 (K alignment of the similarity GEMM)")
         self.saved = None
-        self._tg_off, self._tgN_key, self._consts = None, None, {}
+        self._consts = {}
 
     def _buf(self, name, shape, dtype, zero=False):
         return self.ws.get(f"{self.tag}.{name}", shape, dtype, zero)
@@ -1276,11 +1279,8 @@ class NTXentEngine:
         for k, t, rows, pattern in (("i", img_n, B, 0), ("t", txt_n, B, 0), ("ia", img_all, Np, 1), ("ta", txt_all, Np, 1)):
             bf[k] = self._buf("bf3." + k, (rows, 3 * P), BF16)
             hip.split_bf16(t, t.shape[0], P, rows, pattern, bf[k])
-        tg = self.ws.bufs.get(self.tag + ".targets")
-        if tg is None or tg.numel() != B or self._tg_off != offset:
-            tg = (torch.arange(B, dtype=I64, device=self.ws.device) + offset).contiguous()
-            self.ws.bufs[self.tag + ".targets"] = tg
-            self._tg_off = offset
+        tg = self.ws.cached(self.tag + ".targets", (B, offset),
+                            lambda: (torch.arange(B, dtype=I64, device=self.ws.device) + offset).contiguous())
         lse_r, diag = self._stats(bf["i"], bf["ta"], B, N, tg, "r")
         lse_c, _ = self._stats(bf["t"], bf["ia"], B, N, tg, "c")
         loss = self._buf("loss", (1,), F32)
@@ -1311,12 +1311,10 @@ class NTXentEngine:
         K3 = 3 * P
         cB = self._const("cB", B, c)
         cN = self._const("cN", N, c)
-        tgN = self.ws.bufs.get(self.tag + ".targetsN")
-        if tgN is None or tgN.numel() != N or (off, B) != self._tgN_key:
+        def local_targets():   # column of each gathered row inside this rank's block, -1 outside it
             j = torch.arange(N, dtype=I64, device=self.ws.device) - off
-            tgN = torch.where((j >= 0) & (j < B), j, torch.full_like(j, -1)).contiguous()
-            self.ws.bufs[self.tag + ".targetsN"] = tgN
-            self._tgN_key = (off, B)
+            return torch.where((j >= 0) & (j < B), j, torch.full_like(j, -1)).contiguous()
+        tgN = self.ws.cached(self.tag + ".targetsN", (N, off, B), local_targets)
         # G1[i in loc, j in all] = c (p^r_ij - d_ij);  G2[j in loc, i in all] = c (p^c_ij - d_ij)
         # Each G leaves the DLOGITS epilogue as a hi + lo bf16 pair: at initialisation the embeddings of a batch are
         # nearly parallel, P is nearly uniform and G.T is a difference of nearly equal vectors - a G rounded to bf16

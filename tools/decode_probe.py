@@ -20,7 +20,7 @@ def main():
         pv = torch.randn(R, 1024, device=dev)
         tok = torch.randint(0, 50257, (R,), device=dev)
         eng.trunk.SKINNY_ROWS = skinny
-        eng.__dict__.pop("_graphs", None)
+        eng._graphs.clear()
         print(f"--- rows {R}, {'skinny products' if skinny else 'tile GEMMs'}")
         for graphs in (True,):
             eng.use_graphs = graphs
