@@ -27,6 +27,33 @@ MI355X_DEFAULTS = {
 }
 
 
+RECOMPUTE_MODES = ("none", "mlp", "block")   # engine.GptTrunk.recompute
+
+
+def select_recompute(config) -> str:
+    """Activation-recompute mode of the GPT-2 trunks from a ``Config`` or a plain nested dict: ``mi355x.recompute``
+    (``none | mlp | block``) when present, else the reference's ``hardware.gradient_checkpointing: true`` selects
+    ``"block"`` (keep each layer's input, rebuild the rest in the backward - what ``gradient_checkpointing_enable()`` does
+    per block), else ``"none"``.  ``mi355x.recompute`` has no entry in ``MI355X_DEFAULTS`` on purpose: an absent key must
+    fall through to the reference's switch."""
+    def get(path):
+        cur = getattr(config, "config", config)
+        for key in path.split("."):
+            if not isinstance(cur, dict) or key not in cur:
+                return None
+            cur = cur[key]
+        return cur
+
+    mode = get("mi355x.recompute")
+    if mode is None:
+        return "block" if get("hardware.gradient_checkpointing") is True else "none"
+    if mode is False:      # YAML reads a bare ``none``-like ``off`` / ``false`` as a boolean
+        mode = "none"
+    if mode not in RECOMPUTE_MODES:
+        raise ValueError(f"mi355x.recompute must be one of {RECOMPUTE_MODES}, got {mode!r}")
+    return mode
+
+
 class Config:
     def __init__(self, config_path: Optional[str] = None) -> None:
         if config_path is None:
@@ -58,6 +85,7 @@ class Config:
         "MLFLOW_EXPERIMENT": "logging.mlflow_experiment", "MLFLOW_TRACKING_URI": "logging.mlflow_tracking_uri",
         "CAPTION_ALIGNMENT_NUM_WORKERS": "data.num_workers", "CAPTION_ALIGNMENT_PIN_MEMORY": "data.pin_memory",
         "CAPTION_ALIGNMENT_MIXED_PRECISION": "hardware.mixed_precision",
+        "CAPTION_ALIGNMENT_GRADIENT_CHECKPOINTING": "hardware.gradient_checkpointing",
     }
 
     @staticmethod

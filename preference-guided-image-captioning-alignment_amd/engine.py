@@ -1,9 +1,10 @@
 """Forward/backward schedules of the towers on the HIP kernels (no autograd, no CPU fallback).
 
 Each class owns the launch order of one tower and the activations its backward needs.
-Activations live in a reusable ``Workspace`` sized once per batch geometry (288 GB of HBM:
-everything a backward needs is kept resident, nothing is recomputed except the LM-head
-logits tiles, which never reach HBM in the forward).
+Activations live in a reusable ``Workspace`` sized once per batch geometry.  By default
+everything a backward needs is kept resident (288 GB of HBM); the GPT-2 trunks can instead
+keep less per layer and rebuild it in the backward (``GptTrunk.recompute``).  The LM-head
+logits tiles never reach HBM in the forward and are always recomputed.
 
 Residual streams are f32 (as under the reference's autocast, where LayerNorm outputs and the
 residual adds stay f32); GEMM operands are bf16 with f32 MFMA accumulation.
@@ -328,6 +329,15 @@ class _P:
 
 
 # ------------------------------------------------------------------------------------------ GPT-2 trunk
+RECOMPUTE_MODES = ("none", "mlp", "block")
+
+
+def check_recompute(mode) -> str:
+    if mode not in RECOMPUTE_MODES:
+        raise ValueError(f"recompute must be one of {RECOMPUTE_MODES}, got {mode!r}")
+    return mode
+
+
 @dataclass
 class DecodeState:
     """K/V cache of one incremental decode (``GptTrunk.decode_cache``) and how far it is filled."""
@@ -371,7 +381,21 @@ class GptTrunk:
         self.layer_ranges = [(starts[i], starts[i + 1]) for i in range(arch.layers)]
         self.grad_hook = None  # callable(layer_index) fired when a layer's gradients are complete
         self.overlap_wgrad = True   # weight-gradient launches on a side stream (see backward)
+        self._recompute_mode = "none"
         self._wgrad_stream: Optional[torch.cuda.Stream] = None
+
+    @property
+    def recompute(self) -> str:
+        """Activation recompute of the training forward / backward pair (gradient checkpointing): ``"none"`` keeps
+        every intermediate of every layer, ``"mlp"`` drops ``ln2`` / ``act`` / ``pre`` (half the bytes) and re-runs
+        LayerNorm 2 + ``c_fc`` in the backward, ``"block"`` keeps only each layer's input and re-runs the block up to
+        ``c_fc``.  Same loss and gradients bit for bit in every mode (see ``_layer_fwd``)."""
+        return self._recompute_mode
+
+    @recompute.setter
+    def recompute(self, mode: str) -> None:
+        self._recompute_mode = check_recompute(mode)
+        self.saved = None      # a forward saved under another mode does not have what this mode's backward expects
 
     def _buf(self, name, shape, dtype, zero=False):
         return self.ws.get(f"{self.tag}.{name}", shape, dtype, zero)
@@ -382,7 +406,7 @@ class GptTrunk:
         ``drop(layer, kind)`` (optional) yields the dropout triple of a site (train mode).
         ``pack``: h0 holds the packed rows [pack.Mp, H] instead (``RowPack``): every kernel runs on those rows only, the
         attention takes the sequence offsets, and the dropout sites hash the padded position of each row."""
-        a, H, I = self.arch, self.arch.hidden, self.arch.inner
+        a, H = self.arch, self.arch.hidden
         if S > a.n_pos:
             raise ValueError(f"sequence length {S} exceeds GPT-2's {a.n_pos} learned positions")
         if save and S > ATTN_BWD_MAX_S:
@@ -394,42 +418,86 @@ class GptTrunk:
             mask = pack.mask
         sv = {"M": M, "Bq": Bq, "S": S, "mask": mask, "drop": drop, "pack": pack} if save else None
         h = h0
-        for li, P in enumerate(self.layers):
-            k = f"l{li}." if save else ""
-            ln1 = self._buf(k + "ln1", (M, H), BF16)
-            m1 = self._buf(k + "m1", (M,), F32)
-            r1 = self._buf(k + "r1", (M,), F32)
-            hip.layernorm_fwd(h, M, H, P["ln1w"].w, P["ln1b"].w, a.eps, y_bf16=ln1, mean=m1, rstd=r1)
-            qkv = self._buf(k + "qkv", (M, 3 * H), BF16)
-            hip.gemm(ln1, P["wqkv"].b, M, 3 * H, H, hip.NN, bias=P["bqkv"].w, out_bf16=qkv)
-            att = self._buf(k + "att", (M, H), BF16)
-            lse = self._buf(k + "lse", (rw.nseq, a.heads, S), F32)
-            hip.attention_fwd(qkv, mask, rw.nseq, S, a.heads, True, att, lse, drop=_dsite(drop, li, KIND_ATTN), cu=rw.cu)
-            hm = self._buf(k + "hm", (M, H), F32) if save else h
-            hip.gemm(att, P["wo"].b, M, H, H, hip.NN, bias=P["bo"].w, residual=h, out_f32=hm,
-                     drop=_dsite(drop, li, KIND_RESID_ATTN), drop_rows=rw.ids)
-            ln2 = self._buf(k + "ln2", (M, H), BF16)
-            m2 = self._buf(k + "m2", (M,), F32)
-            r2 = self._buf(k + "r2", (M,), F32)
-            hip.layernorm_fwd(hm, M, H, P["ln2w"].w, P["ln2b"].w, a.eps, y_bf16=ln2, mean=m2, rstd=r2)
-            act = self._buf(k + "act", (M, I), BF16)
-            # training: the epilogue has the sigmoid of gelu_new in registers and leaves gelu_new'(pre) for the backward, whose
-            # data-gradient GEMM then only multiplies (EPI_MUL_AUX) instead of evaluating the sigmoid a second time
-            pre = self._buf(k + "pre", (M, I), BF16) if save else None
-            hip.gemm(ln2, P["wfc"].b, M, I, H, hip.NN,
-                     epilogue=hip.EPI_GELU_NEW_D if (save and self.GELU_PAIR) else hip.EPI_GELU_NEW,
-                     bias=P["bfc"].w, out_bf16=act, aux_out=pre)
-            hn = self._buf(f"l{li + 1}.hin", (M, H), F32) if save else hm
-            hip.gemm(act, P["wpr"].b, M, H, I, hip.NN, bias=P["bpr"].w, residual=hm, out_f32=hn,
-                     drop=_dsite(drop, li, KIND_RESID_MLP), drop_rows=rw.ids)
+        for li in range(len(self.layers)):
+            # a training forward must not overwrite the layer's input (the backward reads it, and under recompute it is
+            # the checkpoint); an evaluation forward runs the residual adds in place
+            hn = self._buf(f"l{li + 1}.hin", (M, H), F32) if save else None
+            s, hn = self._layer_fwd(li, h, rw, mask, S, drop, save, hn=hn)
             if save:
-                sv[li] = dict(hin=h, ln1=ln1, m1=m1, r1=r1, qkv=qkv, att=att, lse=lse, hm=hm, ln2=ln2, m2=m2, r2=r2,
-                              act=act, pre=pre)
+                sv[li] = s if self.recompute == "none" else {k: s[k] for k in self._KEPT[self.recompute]}
             h = hn
         if save:
             sv["hL"] = h
             self.saved = sv
         return h
+
+    # what a training forward keeps of each layer per recompute mode; the backward rebuilds the rest (``_recompute``)
+    _KEPT = {"mlp": ("hin", "ln1", "m1", "r1", "qkv", "att", "lse", "hm", "m2", "r2"), "block": ("hin",)}
+    # operands of the layer's grouped weight-gradient launch (side stream): as scratch they alternate by layer parity
+    _WGRAD_OPERANDS = ("ln1", "att", "ln2", "act")
+
+    def _key(self, li: int, name: str, save: bool) -> str:
+        """Workspace key of buffer ``name`` of layer ``li``: per layer when the backward finds it there (``l{li}.``), one
+        buffer for all layers in an evaluation forward, and ``rc.`` / ``rc{parity}.`` scratch for what the recompute mode
+        rebuilds in the backward (never the keys of the evaluation forward, which may run between the two)."""
+        if not save:
+            return name
+        if self.recompute == "none" or name in self._KEPT[self.recompute]:
+            return f"l{li}.{name}"
+        return (f"rc{li & 1}." if name in self._WGRAD_OPERANDS else "rc.") + name
+
+    def _layer_fwd(self, li: int, h: torch.Tensor, rw: SimpleNamespace, mask, S: int, drop, save: bool,
+                   hn: Optional[torch.Tensor] = None, hm: Optional[torch.Tensor] = None, proj: bool = True):
+        """Launches of block ``li`` on its input ``h``: the forward's, and the backward's when it rebuilds what a
+        recompute mode did not keep - the SAME launches on the same operands, so the rebuilt buffers equal the first
+        pass bit for bit (every dropout site is a counter hash of the padded position).  ``hm`` given: the attention
+        half is skipped (its saved output is ``hm``).  ``proj`` False: stop before ``mlp.c_proj`` (nothing in the
+        backward reads its output).  Returns (buffers of the layer, stream after the block or None)."""
+        a, H, I = self.arch, self.arch.hidden, self.arch.inner
+        P, M = self.layers[li], rw.M
+        s = {"hin": h}
+
+        def buf(name, shape, dtype):
+            s[name] = self._buf(self._key(li, name, save), shape, dtype)
+            return s[name]
+
+        if hm is None:
+            ln1, m1, r1 = buf("ln1", (M, H), BF16), buf("m1", (M,), F32), buf("r1", (M,), F32)
+            hip.layernorm_fwd(h, M, H, P["ln1w"].w, P["ln1b"].w, a.eps, y_bf16=ln1, mean=m1, rstd=r1)
+            qkv = buf("qkv", (M, 3 * H), BF16)
+            hip.gemm(ln1, P["wqkv"].b, M, 3 * H, H, hip.NN, bias=P["bqkv"].w, out_bf16=qkv)
+            att = buf("att", (M, H), BF16)
+            lse = buf("lse", (rw.nseq, a.heads, S), F32)
+            hip.attention_fwd(qkv, mask, rw.nseq, S, a.heads, True, att, lse, drop=_dsite(drop, li, KIND_ATTN), cu=rw.cu)
+            hm = buf("hm", (M, H), F32) if save else h
+            hip.gemm(att, P["wo"].b, M, H, H, hip.NN, bias=P["bo"].w, residual=h, out_f32=hm,
+                     drop=_dsite(drop, li, KIND_RESID_ATTN), drop_rows=rw.ids)
+        s["hm"] = hm
+        ln2, m2, r2 = buf("ln2", (M, H), BF16), buf("m2", (M,), F32), buf("r2", (M,), F32)
+        hip.layernorm_fwd(hm, M, H, P["ln2w"].w, P["ln2b"].w, a.eps, y_bf16=ln2, mean=m2, rstd=r2)
+        act = buf("act", (M, I), BF16)
+        # training: the epilogue has the sigmoid of gelu_new in registers and leaves gelu_new'(pre) for the backward, whose
+        # data-gradient GEMM then only multiplies (EPI_MUL_AUX) instead of evaluating the sigmoid a second time
+        pre = buf("pre", (M, I), BF16) if save else None
+        s["pre"] = pre
+        hip.gemm(ln2, P["wfc"].b, M, I, H, hip.NN,
+                 epilogue=hip.EPI_GELU_NEW_D if (save and self.GELU_PAIR) else hip.EPI_GELU_NEW,
+                 bias=P["bfc"].w, out_bf16=act, aux_out=pre)
+        if not proj:
+            return s, None
+        if hn is None:
+            hn = hm
+        hip.gemm(act, P["wpr"].b, M, H, I, hip.NN, bias=P["bpr"].w, residual=hm, out_f32=hn,
+                 drop=_dsite(drop, li, KIND_RESID_MLP), drop_rows=rw.ids)
+        return s, hn
+
+    def _recompute(self, li: int, sv: dict, rw: SimpleNamespace) -> dict:
+        """Backward, recompute modes: the buffers of layer ``li`` the forward did not keep, rebuilt from its checkpoint
+        (``block``: from ``hin``, 2/3 of the layer's forward GEMM work; ``mlp``: LayerNorm 2 and ``c_fc`` from ``hm``)."""
+        kept = sv[li]
+        s, _ = self._layer_fwd(li, kept["hin"], rw, sv["mask"], sv["S"], sv["drop"], True,
+                               hm=kept.get("hm"), proj=False)
+        return {**s, **kept}
 
     # -- incremental decoding (generation) ---------------------------------------------------------
     SKINNY_ROWS = 32   # up to this many sequences a decode step runs on pgca_gemm_skinny (faster than the tile GEMMs up to 32 rows: DESIGN 5)
@@ -515,7 +583,14 @@ class GptTrunk:
         The grouped weight-gradient launch of a block (192 workgroups of 128 KiB LDS: 192 of the 256 CUs for ~0.85 ms)
         goes to a SIDE stream: nothing in the data-gradient chain of the following blocks depends on it, so their kernels
         run on the 64 CUs it leaves idle instead of waiting behind it.  Its operands that the next block would overwrite
-        (``dpre``, ``dqkv``) alternate between two buffers by layer parity; events order the rest (see below)."""
+        (``dpre``, ``dqkv``) alternate between two buffers by layer parity; events order the rest (see below).
+
+        Recompute modes: the launch's other operands (``ln1``, ``att``, ``ln2``, ``act``) are per-layer buffers only as far
+        as the mode keeps them; those it rebuilds are scratch, and the rebuild of layer ``li - 1`` runs on the main stream
+        while the launch of layer ``li`` may still be reading.  Rule: scratch that the side stream reads alternates by
+        layer parity exactly like ``dpre`` / ``dqkv`` (``_key``: ``rc0.`` / ``rc1.``), and layer ``li`` is rebuilt only
+        AFTER ``settle(li + 2)``, the one wait that already frees that parity.  Scratch only the main stream reads
+        (``qkv``, ``lse``, ``hm``, ``pre``, row statistics: ``rc.``) is a single buffer, ordered by the stream itself."""
         sv = self.saved
         assert sv is not None, "forward(save=True) must precede backward"
         a, H, I = self.arch, self.arch.hidden, self.arch.inner
@@ -544,9 +619,10 @@ class GptTrunk:
                     self.grad_hook(layer)
 
         for li in range(L - 1, -1, -1):
-            P, s = self.layers[li], sv[li]
+            P = self.layers[li]
             par = "1" if (li & 1) else "0"
-            settle(li + 2)   # that launch read dpre / dqkv of this parity
+            settle(li + 2)   # that launch read dpre / dqkv (and the recompute scratch) of this parity
+            s = sv[li] if self.recompute == "none" else self._recompute(li, sv, rw)
             # ---- MLP: h_out = hm + c_proj(gelu(c_fc(ln2(hm))))
             dpre = self._buf("dpre" + par, (M, I), BF16)
             # the same GEMM leaves the column sums of dpre per 64-row block: mlp.c_fc's bias gradient without a second

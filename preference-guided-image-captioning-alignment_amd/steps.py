@@ -119,8 +119,12 @@ class DPOStep:
     def __init__(self, store: ParamStore, ws: Workspace, vit: VisionTower, vhead: ProjHead,
                  dec: CaptionDecoderEngine, beta: float = 0.1, reference_free: bool = False,
                  label_smoothing: float = 0.0, reduce: Optional[str] = None, ref: Optional[ReferencePolicy] = None,
-                 ref_side_stream: bool = False, dropout: Optional[DropoutPlan] = None, packed: bool = True):
+                 ref_side_stream: bool = False, dropout: Optional[DropoutPlan] = None, packed: bool = True,
+                 recompute: str = "none"):
         self.store, self.ws, self.vit, self.vhead, self.dec = store, ws, vit, vhead, dec
+        # activation recompute of the policy trunk's training forward / backward (engine.GptTrunk.recompute); the frozen
+        # reference policy and every evaluation forward keep nothing anyway
+        dec.trunk.recompute = recompute
         self.beta, self.reference_free, self.ls = float(beta), bool(reference_free), float(label_smoothing)
         # trainer parity: 2-forward == PreferenceLoss (length-mean); 4-forward == DPOPreferenceLoss (length-sum)
         self.reduce = reduce or ("mean" if reference_free else "sum")
@@ -218,8 +222,9 @@ class ContrastiveStep:
 
     def __init__(self, store: ParamStore, ws: Workspace, vit: VisionTower, vhead: ProjHead, text: TextTowerEngine,
                  temperature: float, dp=None, global_negatives: bool = False, dropout: Optional[DropoutPlan] = None,
-                 packed: bool = True):
+                 packed: bool = True, recompute: str = "none"):
         self.store, self.ws, self.vit, self.vhead, self.text = store, ws, vit, vhead, text
+        text.trunk.recompute = recompute   # activation recompute of the text tower's trunk (engine.GptTrunk.recompute)
         self.packed = bool(packed)   # text tower on the real tokens' rows only (engine.RowPack)
         self.dropout = dropout if dropout is not None else DropoutPlan(0.0)
         self.ntx = NTXentEngine(ws, store.arch.proj_dim, temperature)

@@ -35,6 +35,7 @@ from typing import Any, Dict, Iterable, List, Optional
 
 import torch
 
+from .config import select_recompute
 from .dist import DataParallel, OverlappedTrunkReducer
 from .engine import DropoutPlan
 from .input import BatchPrefetcher
@@ -58,6 +59,8 @@ class PreferenceGuidedTrainer:
                          or config.get("training.stage1.gradient_accumulation_steps", 4))
         self.temperature = float(config.get("model.temperature", 0.07))
         self.beta = float(config.get("training.stage2.dpo_beta", 0.1))
+        # mi355x.recompute, else the reference's hardware.gradient_checkpointing (config.select_recompute)
+        self.recompute = select_recompute(config)
         self.current_stage, self.global_step, self.epoch = 1, 0, 0
         self.best_val_loss, self.patience_counter = float("inf"), 0
         self._resume: Optional[Dict[str, Any]] = None   # optimiser / scheduler / dropout state of a loaded checkpoint
@@ -180,7 +183,8 @@ class PreferenceGuidedTrainer:
         step = ContrastiveStep(m.store, m.ws, m.vision_encoder.tower, m.vision_encoder.head, m.text_encoder.engine,
                                self.temperature, dp=self.dp,
                                global_negatives=bool(self.config.get("mi355x.stage1.global_negatives", False)),
-                               dropout=self._dropout_plan(1), packed=bool(self.config.get("mi355x.packed_rows", True)))
+                               dropout=self._dropout_plan(1), packed=bool(self.config.get("mi355x.packed_rows", True)),
+                               recompute=self.recompute)
         reducer = OverlappedTrunkReducer(self.dp, m.text_encoder.engine.trunk,
                                          group=int(self.config.get("mi355x.allreduce_layer_group", 4)))
         extra = [s for s in opt.segments if s is not reducer.seg]
@@ -209,7 +213,8 @@ class PreferenceGuidedTrainer:
         step = DPOStep(m.store, m.ws, m.vision_encoder.tower, m.vision_encoder.head, m.caption_decoder.engine,
                        beta=self.beta, reference_free=reference_free,
                        label_smoothing=float(self.config.get("mi355x.dpo.label_smoothing", 0.0)), ref=ref,
-                       dropout=self._dropout_plan(2), packed=bool(self.config.get("mi355x.packed_rows", True)))
+                       dropout=self._dropout_plan(2), packed=bool(self.config.get("mi355x.packed_rows", True)),
+                       recompute=self.recompute)
         reducer = OverlappedTrunkReducer(self.dp, m.caption_decoder.engine.trunk,
                                          group=int(self.config.get("mi355x.allreduce_layer_group", 4)))
         extra = [s for s in opt.segments if s is not reducer.seg]

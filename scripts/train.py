@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Train the two stages on MI355X with the reference's command line
-(reference scripts/train.py:253-294: --config --resume --stage {1,2} --output-dir --log-level --dry-run).
+(reference scripts/train.py:253-294: --config --resume --stage {1,2} --output-dir --log-level --dry-run; plus --synthetic-samples and --recompute).
 
 Data loading is outside the hot path: batches come from seeded synthetic datasets with the reference's
 batch-dict contract (loader.py:252-258,487-497; the reference's own dummy loader, scripts/train.py:194-241),
@@ -70,6 +70,9 @@ def main():
     ap.add_argument("--log-level", type=str, default="INFO", choices=["DEBUG", "INFO", "WARNING", "ERROR"])
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--synthetic-samples", type=int, default=256)
+    ap.add_argument("--recompute", type=str, choices=["none", "mlp", "block"], default=None,
+                    help="activation recompute of the GPT-2 trunks (overrides mi355x.recompute / "
+                         "hardware.gradient_checkpointing)")
     args = ap.parse_args()
 
     logging.basicConfig(level=getattr(logging, args.log_level), format="%(asctime)s %(name)s %(levelname)s %(message)s")
@@ -77,6 +80,8 @@ def main():
     cfg = Config(args.config)
     if args.output_dir:
         cfg.set("paths.output_dir", args.output_dir)
+    if args.recompute is not None:
+        cfg.set("mi355x.recompute", args.recompute)
     seed = int(cfg.get("training.seed", 42))
     set_random_seeds(seed)
     dp = DataParallel.init_from_env()

@@ -190,10 +190,11 @@ LENS, S = (8, 5, 3), 8
 
 
 # ---------------------------------------------------------------------------------------------------------------- scenarios
-def trunk(packed: bool, drop: bool):
+def trunk(packed: bool, drop: bool, recompute: str = "none"):
     def run():
         ws, st = T.ws(), T.store()
         tr = E.GptTrunk(st, "text_encoder.text_model", ARCH.gpt, ws, "t.trunk")
+        tr.recompute = recompute
         sb = seq_batch(LENS, S, packed)
         M, H = (sb.pack.Mp if packed else sb.Bq * S), ARCH.gpt.hidden
         h0, g, g_bf = _randn("h0", M, H), _randn("g", M, H), _randn("g_bf", M, H, dtype=BF16)
@@ -315,6 +316,7 @@ def ntxent():
 
 SCENARIOS = [(f"trunk_{'packed' if p else 'padded'}_{'drop' if d else 'nodrop'}", trunk(p, d))
              for p in (False, True) for d in (False, True)]
+SCENARIOS += [(f"trunk_packed_drop_{m}", trunk(True, True, m)) for m in ("mlp", "block")]   # activation recompute
 SCENARIOS += [("vit_frozen", vit(False)), ("vit_trainable", vit(True))]
 SCENARIOS += [(f"decoder_{'packed' if p else 'padded'}_{'drop' if d else 'nodrop'}", decoder(p, d, "mean" if p else "sum"))
               for p in (False, True) for d in (False, True)]
