@@ -36,7 +36,7 @@ typedef enum pgca_status {
   PGCA_ERR_LAUNCH = -2   /* hipLaunch failed; see pgca_last_error() */
 } pgca_status;
 
-#define PGCA_ABI_VERSION 304 /* bumped whenever a signature or struct layout below changes */
+#define PGCA_ABI_VERSION 305 /* bumped whenever a signature or struct layout below changes */
 int pgca_version(void);        /* == PGCA_ABI_VERSION of the header the library was built from */
 int pgca_sizeof_gemm_args(void); /* sizeof(pgca_gemm_args) as compiled: bindings compare it with their own layout */
 const char* pgca_last_error(void);
@@ -425,6 +425,40 @@ int pgca_split_bf16(const float* x, int32_t R, int32_t P, int32_t rows_out, int3
 int pgca_axpy(const float* x, float alpha, float* y, int64_t n, int32_t accumulate, void* stream);
 /* gather / scatter rows of an f32 or bf16 [*, H] matrix by int32 row_map. */
 int pgca_gather_rows_bf16(const void* src, const int32_t* row_map, int32_t M, int32_t H, void* dst, void* stream);
+
+/* ------------------------------------------------------------------ token selection (generation) */
+/* One token per row of logits [R, ld] f32 (ld % 4 == 0, 16-B aligned base; columns >= V ignored), replacing the torch
+ * chain after the LM head in CaptionDecoder.generate (model.py:621-678 -> HF logits processors + sampling).
+ * Processors in HF's order, exactly CaptionDecoder._process_scores:
+ *   repetition penalty on the raw score (s < 0 ? s * p : s / p), once per DISTINCT id of prev[r, 0 .. n_prev)
+ *   (int64 [R, ld_prev]; n_prev may be 0); then, only when sampling (u != NULL): temperature (divide), top-k
+ *   (0 = off; scores strictly below the k-th largest go, ties with it stay; top_k >= V is off), top-p (ascending, a
+ *   class of equal scores goes iff the cumulative probability up to and including it is <= 1 - top_p; the largest
+ *   always stays).
+ * u == NULL: argmax of the penalised scores, lowest id among equals.  Otherwise u [R] f32 in (0, 1): inverse CDF over
+ * the kept tokens in token-id order - the smallest j whose kept prefix mass >= u * Z_kept.
+ * next [R] int64; next_logp [R] = log-softmax of the RAW logits at the chosen token.  done (optional, uint8 [R]): a
+ * non-zero row yields pad_id and 0.  One workgroup per row, no sort, fixed-order sums: bit-identical from run to run.
+ * With a penalty, ceil(V / 32) * 4 bytes of LDS hold the seen-id bitmask (V <= 491 520). */
+int pgca_select_token(const float* logits, int32_t ld, int32_t V, int32_t R, const int64_t* prev, int32_t ld_prev,
+                      int32_t n_prev, float repetition_penalty, float temperature, int32_t top_k, float top_p,
+                      const float* u, const uint8_t* done, int64_t pad_id, int64_t* next, float* next_logp,
+                      void* stream);
+/* Beam-search candidates of B batch items with nb beams each (logits [B * nb, ld]), replacing the per-step
+ * log_softmax -> processors -> + running_beam_scores -> topk / multinomial of HF's _beam_search: the processors above
+ * act on the LOG-PROBABILITIES of each row (temperature / top-k / top-p only when warp != 0), acc = processed +
+ * beam_scores[b * nb + beam]; the K (<= 64; 2 * nb) candidates with the largest key come out in descending key order,
+ * equal keys by ascending flat index: cand_score [B, K] = acc, cand_index [B, K] int64 = beam * V + token.
+ * use_noise == 0: key = acc.  Otherwise key = acc + g with Gumbel noise g = -log(-log u),
+ *   u = ((hash32(f * 0x9E3779B1 + noise_seed) >> 8) + 0.5) * 2^-24,  f = (b * nb + beam) * V + token  (mod 2^32),
+ * hash32 = the lowbias32 function of the dropout masks: the order is then the draw order of sampling K candidates
+ * without replacement from softmax(acc) (beam-sample).  Fewer than K finite keys: the tail carries -inf and the
+ * lowest unused flat indices.  nb <= 32, nb * V < 2^24; with a penalty nb * ceil(V / 32) * 4 bytes of LDS <= 60 KiB. */
+int pgca_select_beam_candidates(const float* logits, int32_t ld, int32_t V, int32_t B, int32_t nb, const int64_t* prev,
+                                int32_t ld_prev, int32_t n_prev, float repetition_penalty, int32_t warp,
+                                float temperature, int32_t top_k, float top_p, const float* beam_scores, int32_t K,
+                                int32_t use_noise, uint32_t noise_seed, float* cand_score, int64_t* cand_index,
+                                void* stream);
 
 #ifdef __cplusplus
 }

@@ -114,10 +114,13 @@ _SIGS = {
     "pgca_split_bf16": [_vp, _i32, _i32, _i32, _i32, _vp, _vp],
     "pgca_axpy": [_vp, _f32, _vp, _i64, _i32, _vp],
     "pgca_gather_rows_bf16": [_vp, _vp, _i32, _i32, _vp, _vp],
+    "pgca_select_token": [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _f32, _i32, _f32, _vp, _vp, _i64, _vp, _vp, _vp],
+    "pgca_select_beam_candidates": [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _i32, _f32, _i32, _f32, _vp, _i32,
+                                    _i32, C.c_uint32, _vp, _vp, _vp],
 }
 EXPORTS = ["pgca_version", "pgca_last_error", "pgca_sizeof_gemm_args", "pgca_sizeof_skinny_args",
            "pgca_gemm_skinny_workspace"] + list(_SIGS)
-ABI_VERSION = 304  # include/pgca_hip.h PGCA_ABI_VERSION
+ABI_VERSION = 305  # include/pgca_hip.h PGCA_ABI_VERSION
 
 _lib = None
 
@@ -397,6 +400,24 @@ def logits_logprob_bwd(logits, ld, V, row_map, targets, g, R, dlogits):
 def logits_logprob(logits, ld, V, row_map, targets, R, out):
     _check(load().pgca_logits_logprob(_p(logits), ld, V, _p(row_map), _p(targets), R, _p(out), _stream()),
            "pgca_logits_logprob")
+
+
+# --------------------------------------------------------------------------- token selection (generation)
+def select_token(logits, V, R, prev, n_prev, repetition_penalty, temperature, top_k, top_p, u, done, pad_id, next_ids,
+                 next_logp):
+    """``logits`` [R, >= V] f32 rows (row stride % 4 == 0), ``prev`` [R, >= n_prev] int64 rows; see pgca_hip.h."""
+    _check(load().pgca_select_token(_p(logits), logits.stride(0), V, R, _p(prev), prev.stride(0) if n_prev else 0, n_prev,
+                                    repetition_penalty, temperature, top_k, top_p, _p(u), _p(done), pad_id, _p(next_ids),
+                                    _p(next_logp), _stream()), "pgca_select_token")
+
+
+def select_beam_candidates(logits, V, B, nb, prev, n_prev, repetition_penalty, warp, temperature, top_k, top_p,
+                           beam_scores, K, use_noise, noise_seed, cand_score, cand_index):
+    _check(load().pgca_select_beam_candidates(_p(logits), logits.stride(0), V, B, nb, _p(prev),
+                                              prev.stride(0) if n_prev else 0, n_prev, repetition_penalty, int(warp),
+                                              temperature, top_k, top_p, _p(beam_scores), K, int(use_noise),
+                                              noise_seed & 0xFFFFFFFF, _p(cand_score), _p(cand_index), _stream()),
+           "pgca_select_beam_candidates")
 
 
 def dpo_loss(pol_w, pol_l, ref_w, ref_l, B, beta, label_smoothing, loss, dpol_w=None, dpol_l=None, metrics=None):

@@ -211,10 +211,11 @@ class CaptionDecoder:
 
     @staticmethod
     def _process_scores(scores: torch.Tensor, ids: torch.Tensor, repetition_penalty: float, warp: bool,
-                        temperature: float, top_p: float) -> torch.Tensor:
+                        temperature: float, top_p: float, top_k: int = 0) -> torch.Tensor:
         """HF's logits processors in HF's order (generation/logits_process.py): RepetitionPenaltyLogitsProcessor, then -
-        when sampling - TemperatureLogitsWarper and TopPLogitsWarper (keeps the smallest set with mass >= top_p, at
-        least one token).  ``scores`` are raw logits for greedy / sampling and log-probabilities for beam search."""
+        when sampling - TemperatureLogitsWarper, TopKLogitsWarper (scores below the k-th largest go; 0 = off) and
+        TopPLogitsWarper (keeps the smallest set with mass >= top_p, at least one token).  ``scores`` are raw logits for
+        greedy / sampling and log-probabilities for beam search."""
         if repetition_penalty != 1.0 and ids.shape[1]:
             seen = torch.gather(scores, 1, ids)
             seen = torch.where(seen < 0, seen * repetition_penalty, seen / repetition_penalty)
@@ -222,6 +223,9 @@ class CaptionDecoder:
         if warp:
             if temperature != 1.0:
                 scores = scores / float(temperature)
+            if 0 < top_k < scores.shape[-1]:
+                kth = torch.topk(scores, int(top_k), dim=-1)[0][:, -1:]
+                scores = scores.masked_fill(scores < kth, float("-inf"))
             if top_p < 1.0:
                 srt, idx = torch.sort(scores, dim=-1, descending=False)
                 cum = torch.softmax(srt, dim=-1).cumsum(dim=-1)
@@ -235,7 +239,7 @@ class CaptionDecoder:
                  temperature: float = 1.0, do_sample: bool = True, top_p: float = 0.9,
                  repetition_penalty: float = 1.1, pad_token_id: Optional[int] = None,
                  eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
-                 use_cache: bool = True, **kwargs) -> torch.Tensor:
+                 use_cache: bool = True, top_k: int = 0, selection: str = "torch", **kwargs) -> torch.Tensor:
         """Reference ``CaptionDecoder.generate`` (model.py:621-678): HF ``generate`` started from the single embedding
         ``vision_projection(vision_features)``.  Same arguments; returns the generated ids ``[B, <= max_length - 1]``
         (int64; HF counts the prefix embedding as one of the ``max_length`` positions, generation/utils.py
@@ -249,9 +253,17 @@ class CaptionDecoder:
         distribution: torch's RNG stream differs).  Token ids default to the decoder tokenizer's (model.py:509-511:
         [PAD] = vocab, [EOS] = vocab + 2).  ``use_cache`` (HF's default): every step feeds ONE position through the trunk
         against per-layer K/V buffers (``engine.GptTrunk.decode_step``); ``False`` recomputes the prefix each step (the
-        cross-check)."""
+        cross-check).
+
+        ``top_k`` (0 = off) is HF's TopKLogitsWarper, applied when sampling.  ``selection``: ``"torch"`` (default) runs
+        the processors, the draw and the candidate ranking as torch ops; ``"device"`` runs them in the HIP selection
+        kernels (``hip.select_token`` / ``hip.select_beam_candidates``): the same ids for greedy and deterministic beam
+        search, the same distributions - from a different random stream - when sampling."""
         if kwargs:
             raise TypeError(f"unsupported generation arguments: {sorted(kwargs)}")
+        if selection not in ("torch", "device"):
+            raise ValueError(f"selection={selection!r}: expected 'torch' or 'device'")
+        top_k = max(0, int(top_k))
         eng, dev = self.engine, self._o.device
         base = self._o.arch.gpt.base_vocab
         pad = base if pad_token_id is None else int(pad_token_id)
@@ -264,7 +276,11 @@ class CaptionDecoder:
         pv = eng.prefix_embedding(emb)
         if nb > 1:
             return self._beam_search(pv, B, nb, L, pad, eos, float(temperature), bool(do_sample), float(top_p),
-                                     float(repetition_penalty), generator, use_cache)
+                                     float(repetition_penalty), generator, use_cache, top_k, selection == "device")
+        if selection == "device":
+            ids_buf, n = self._decode_device(pv, L, pad, eos, float(temperature), bool(do_sample), top_k, float(top_p),
+                                             float(repetition_penalty), generator, use_cache)[:2]
+            return self._trim(ids_buf, n, pad)
         # ---- greedy / sampling (HF _sample): preallocated ids, one EOS read-back every EOS_CHECK tokens
         ids_buf = torch.full((B, L), pad, dtype=I64, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
@@ -274,7 +290,7 @@ class CaptionDecoder:
             ids = ids_buf[:, :n]
             if not use_cache:
                 logits = eng.next_token_logits(pv, ids)
-            scores = self._process_scores(logits.clone(), ids, repetition_penalty, do_sample, temperature, top_p)
+            scores = self._process_scores(logits.clone(), ids, repetition_penalty, do_sample, temperature, top_p, top_k)
             if do_sample:
                 nxt = torch.multinomial(torch.softmax(scores, dim=-1), 1, generator=generator)[:, 0]
             else:
@@ -287,13 +303,50 @@ class CaptionDecoder:
                 break
             if use_cache:
                 logits = eng.decode_advance(nxt)
+        return self._trim(ids_buf, n, pad)
+
+    @staticmethod
+    def _trim(ids_buf, n, pad):
         # columns generated after every sequence had finished are all [PAD]: trimming them equals stopping at once
         alive = (ids_buf[:, :n] != pad).any(dim=0)
         last_tok = int(alive.nonzero().max()) + 1 if bool(alive.any()) else 1
         return ids_buf[:, :max(1, min(n, last_tok))]
 
+    def _decode_device(self, pv, L, pad, eos, temperature, do_sample, top_k, top_p, repetition_penalty, generator,
+                       use_cache=True):
+        """The greedy / sampling loop of ``generate`` with one ``hip.select_token`` launch per step in place of the
+        torch processors and draw (one uniform per row and step from ``generator``).  Returns (ids_buf [R, L], columns
+        filled, logp [R] = sum of the model's own log-probability of every generated token, [EOS] included and [PAD]
+        excluded, lengths [R] = how many tokens that is)."""
+        eng, dev = self.engine, self._o.device
+        R = pv.shape[0]
+        ids_buf = torch.full((R, L), pad, dtype=I64, device=dev)
+        done = torch.zeros(R, dtype=torch.bool, device=dev)
+        nxt = torch.empty(R, dtype=I64, device=dev)
+        step_lp = torch.empty(R, dtype=F32, device=dev)
+        logp = torch.zeros(R, dtype=F32, device=dev)
+        lengths = torch.zeros(R, dtype=I64, device=dev)
+        n = 0
+        logits = eng.decode_begin(pv, L) if use_cache else None
+        while True:
+            if not use_cache:
+                logits = eng.next_token_logits(pv, ids_buf[:, :n])
+            u = torch.rand(R, generator=generator, device=dev) if do_sample else None
+            hip.select_token(logits, logits.shape[1], R, ids_buf, n, repetition_penalty, temperature, top_k, top_p, u, done, pad, nxt,
+                             step_lp)
+            ids_buf[:, n] = nxt
+            logp += step_lp
+            lengths += ~done
+            n += 1
+            done = done | (nxt == eos)
+            if n == L or ((n % self.EOS_CHECK == 0) and bool(done.all())):
+                break
+            if use_cache:
+                logits = eng.decode_advance(nxt)
+        return ids_buf, n, logp, lengths
+
     def _beam_search(self, pv, B, nb, L, pad, eos, temperature, do_sample, top_p, repetition_penalty, generator,
-                     use_cache) -> torch.Tensor:
+                     use_cache, top_k=0, device_select=False) -> torch.Tensor:
         """HF ``GenerationMixin._beam_search`` (transformers 5.x, generation/utils.py) for ``length_penalty`` 1.0,
         ``early_stopping`` False, one returned sequence: state tensors and update rules carry HF's names."""
         eng, dev = self.engine, self._o.device
@@ -310,20 +363,31 @@ class CaptionDecoder:
         gen_len = torch.zeros(B, nb, dtype=I64, device=dev)      # tokens of each finished hypothesis (HF: beam_indices)
         ar = torch.arange(B, device=dev)[:, None]
         cur = 0
+        if device_select and do_sample:                          # one noise seed per step, read back once
+            seeds = torch.randint(0, 2 ** 31 - 1, (L,), generator=generator, device=dev).tolist()
         logits = eng.decode_begin(pvr, L) if use_cache else None
         while True:
             flat = running_sequences.view(R, L)[:, :cur]
             if not use_cache:
                 logits = eng.next_token_logits(pvr, flat)
-            log_probs = torch.log_softmax(logits.float(), dim=-1)
-            log_probs = self._process_scores(log_probs, flat, repetition_penalty, do_sample, temperature, top_p)
-            V = log_probs.shape[1]
-            acc = (log_probs.view(B, nb, V) + running_beam_scores[:, :, None]).view(B, nb * V)
-            if do_sample:                                        # beam-sample: candidates drawn, then ranked by score
-                idx = torch.multinomial(torch.softmax(acc, dim=-1), num_samples=K2, generator=generator)
-                topk_log_probs = torch.gather(acc, 1, idx)
+            V = logits.shape[1]
+            if device_select:                                    # one launch: processors, accumulation, ranking / draw
+                seed = seeds[cur] if do_sample else 0
+                topk_log_probs = torch.empty(B, K2, dtype=F32, device=dev)
+                idx = torch.empty(B, K2, dtype=I64, device=dev)
+                hip.select_beam_candidates(logits, V, B, nb, running_sequences.view(R, L), cur, repetition_penalty,
+                                           do_sample, temperature, top_k, top_p, running_beam_scores.contiguous(), K2,
+                                           do_sample, seed, topk_log_probs, idx)
             else:
-                topk_log_probs, idx = torch.topk(acc, k=K2)
+                log_probs = torch.log_softmax(logits.float(), dim=-1)
+                log_probs = self._process_scores(log_probs, flat, repetition_penalty, do_sample, temperature, top_p,
+                                                 top_k)
+                acc = (log_probs.view(B, nb, V) + running_beam_scores[:, :, None]).view(B, nb * V)
+                if do_sample:                                    # beam-sample: candidates drawn, then ranked by score
+                    idx = torch.multinomial(torch.softmax(acc, dim=-1), num_samples=K2, generator=generator)
+                    topk_log_probs = torch.gather(acc, 1, idx)
+                else:
+                    topk_log_probs, idx = torch.topk(acc, k=K2)
             src_beam = idx // V
             topk_running = running_sequences[ar, src_beam]      # [B, 2nb, L]
             topk_ids = idx % V
@@ -474,6 +538,38 @@ class PreferenceGuidedCaptioningModel:
         try:
             emb = self.vision_encoder(images)["embeddings"]
             return self.caption_decoder.generate(vision_features=emb, **gen_kwargs)
+        finally:
+            self.train(was)
+
+    @torch.no_grad()
+    def generate_candidates(self, images: torch.Tensor, num_candidates: int, max_length: int = 50,
+                            temperature: float = 1.0, top_p: float = 0.9, top_k: int = 0,
+                            repetition_penalty: float = 1.1, generator: Optional[torch.Generator] = None,
+                            use_cache: bool = True):
+        """Best-of-N sampling, the step that turns a Stage-1 model into Stage-2 preference data: ``num_candidates``
+        sampled captions per image with the model's own log-probability of each.  Returns ``(ids [B, n, L] int64,
+        logp [B, n] f32, lengths [B, n] int64)``: ``logp`` sums the log-softmax of the raw logits over the generated
+        tokens, [EOS] included and [PAD] excluded; ``lengths`` counts the same tokens.  Device-side selection;
+        ``use_cache`` as in ``generate``."""
+        n = int(num_candidates)
+        if n < 1:
+            raise ValueError(f"num_candidates={num_candidates}: expected at least 1")
+        L = int(max_length) - 1
+        if L < 1:
+            raise ValueError(f"max_length={max_length} leaves no room for a generated token (the prefix counts as one)")
+        was = self.training
+        self.eval()
+        try:
+            dec = self.caption_decoder
+            base = self.arch.gpt.base_vocab
+            emb = self.vision_encoder(images)["embeddings"]
+            B = emb.shape[0]
+            pv = dec.engine.prefix_embedding(emb.to(self.device, F32).contiguous()).repeat_interleave(n, dim=0)
+            ids_buf, cols, logp, lengths = dec._decode_device(pv, L, base, base + 2, float(temperature), True,
+                                                              max(0, int(top_k)), float(top_p), float(repetition_penalty),
+                                                              generator, use_cache)
+            ids = dec._trim(ids_buf, cols, base)
+            return ids.reshape(B, n, -1).contiguous(), logp.view(B, n), lengths.view(B, n)
         finally:
             self.train(was)
 

@@ -3,7 +3,7 @@
 configs/default.yaml:92, measured the reference's way - evaluation/metrics.py:863-893: wall time of one
 ``generate_captions``-style call divided by the images in the batch).
 
-    python tools/gen_latency.py [--runs 20] [--max-length 50] [--out profiles/r03_generation_latency.json]
+    python tools/gen_latency.py [--runs 20] [--max-length 50] [--selection torch|device] [--out FILE.json]
 
 Full-size ViT-B/32 + GPT-2-Medium decoder with seeded random weights (no tokenizer / checkpoints offline: the token
 ids are produced, the string decode is not part of the number), images resident on the device.  Modes: the reference's
@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--max-length", type=int, default=50)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-cache-free", action="store_true")
+    ap.add_argument("--selection", choices=("torch", "device"), default="torch",
+                    help="token selection after the LM head: torch ops (default) or the HIP selection kernels")
     a = ap.parse_args()
     from pgca_amd.model import PreferenceGuidedCaptioningModel
     dev = torch.device("cuda:0")
@@ -41,10 +43,11 @@ def main():
     # random weights never emit [EOS]: every caption runs to max_length, the worst case for latency
     res = {"model": "CLIP-ViT-B/32 + GPT-2-M decoder, random init", "max_length": a.max_length, "runs": a.runs,
            "definition": "wall time of one batch call / images in the batch (reference evaluation/metrics.py:863-893)",
-           "target_p95_ms": 150.0, "cases": []}
+           "target_p95_ms": 150.0, "selection": a.selection, "cases": []}
     modes = [("reference defaults: 4 beams, do_sample, top_p 0.9, repetition 1.1",
               dict(num_beams=4, do_sample=True, top_p=0.9, repetition_penalty=1.1)),
              ("greedy", dict(num_beams=1, do_sample=False, repetition_penalty=1.1))]
+    sel = {} if a.selection == "torch" else {"selection": a.selection}
     for B in (1, 32):
         img = torch.randn(B, 3, 224, 224, device=dev)
         for label, kw in modes:
@@ -56,11 +59,11 @@ def main():
                 for r in range(a.runs + 2):
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    ids = model.generate_token_ids(img, max_length=a.max_length, generator=gen, use_cache=cache, **kw)
+                    ids = model.generate_token_ids(img, max_length=a.max_length, generator=gen, use_cache=cache, **kw, **sel)
                     torch.cuda.synchronize()
                     if r >= 2:                    # two warm-up calls (buffer allocation)
                         lat.append(1e3 * (time.perf_counter() - t0))
-                case = {"batch": B, "mode": label, "kv_cache": cache, "tokens": int(ids.shape[1]),
+                case = {"batch": B, "mode": label, "kv_cache": cache, "selection": a.selection, "tokens": int(ids.shape[1]),
                         "call_ms_p50": pct(lat, 0.5), "call_ms_p95": pct(lat, 0.95),
                         "per_caption_ms_p50": pct(lat, 0.5) / B, "per_caption_ms_p95": pct(lat, 0.95) / B}
                 res["cases"].append(case)
