@@ -36,7 +36,7 @@ typedef enum pgca_status {
   PGCA_ERR_LAUNCH = -2   /* hipLaunch failed; see pgca_last_error() */
 } pgca_status;
 
-#define PGCA_ABI_VERSION 305 /* bumped whenever a signature or struct layout below changes */
+#define PGCA_ABI_VERSION 306 /* bumped whenever a signature or struct layout below changes */
 int pgca_version(void);        /* == PGCA_ABI_VERSION of the header the library was built from */
 int pgca_sizeof_gemm_args(void); /* sizeof(pgca_gemm_args) as compiled: bindings compare it with their own layout */
 const char* pgca_last_error(void);
@@ -459,6 +459,59 @@ int pgca_select_beam_candidates(const float* logits, int32_t ld, int32_t V, int3
                                 float temperature, int32_t top_k, float top_p, const float* beam_scores, int32_t K,
                                 int32_t use_noise, uint32_t noise_seed, float* cand_score, int64_t* cand_index,
                                 void* stream);
+/* The two entries above with HF's banning processors (NoRepeatNGram, MinLength / MinNewTokensLength, SuppressTokens):
+ * a banned token's processed score is -inf whatever the repetition penalty made of it, so it drops out of argmax,
+ * top-k, top-p, the draw and the beam keys (cand_score -inf).  next_logp and the beam kernel's log-softmax stay those
+ * of the RAW row (HF normalises before the processors run).
+ *   no_repeat_ngram_size n (0 = off): in a row with n_prev >= n - 1 previous ids, token prev[i + n - 1] is banned for
+ *     every i with prev[i .. i + n - 2] == prev[n_prev - n + 1 .. n_prev - 1]; n == 1 bans every seen id; shorter rows
+ *     ban nothing.
+ *   ban_ids [n_ban] (device int64): banned in every row (suppress_tokens; the caller adds [EOS] while the sequence is
+ *     shorter than the minimum length).  Ids outside [0, V) are ignored in both.
+ * A row with every token banned yields the lowest id (token kernel; next_logp of that id) and -inf candidates with the
+ * lowest flat indices (beam kernel).  The banned ids are a second bitmask next to the seen ids: with a penalty AND bans
+ * 2 * rows * ceil(V / 32) * 4 bytes of LDS (rows = 1, or nb for the beam kernel) must fit 61 440 bytes - nb <= 4 at
+ * V <= 61 440 - else PGCA_ERR_INVALID is returned and nothing is launched.  Empty options (all zero) give exactly the
+ * entries above, which call these. */
+typedef struct pgca_select_opts {
+  int32_t no_repeat_ngram_size;
+  int32_t n_ban;
+  const int64_t* ban_ids;
+} pgca_select_opts;
+int pgca_sizeof_select_opts(void);
+int pgca_select_token_ex(const float* logits, int32_t ld, int32_t V, int32_t R, const int64_t* prev, int32_t ld_prev,
+                         int32_t n_prev, float repetition_penalty, float temperature, int32_t top_k, float top_p,
+                         const float* u, const uint8_t* done, int64_t pad_id, int64_t* next, float* next_logp,
+                         const pgca_select_opts* opts, void* stream);
+int pgca_select_beam_candidates_ex(const float* logits, int32_t ld, int32_t V, int32_t B, int32_t nb,
+                                   const int64_t* prev, int32_t ld_prev, int32_t n_prev, float repetition_penalty,
+                                   int32_t warp, float temperature, int32_t top_k, float top_p,
+                                   const float* beam_scores, int32_t K, int32_t use_noise, uint32_t noise_seed,
+                                   float* cand_score, int64_t* cand_index, const pgca_select_opts* opts, void* stream);
+/* The rest of one step of HF's _beam_search (generation/utils.py, transformers 5.x) once the K = 2 * nb candidates of
+ * every batch item are known (cand_score / cand_index [B, K] as pgca_select_beam_candidates writes them): the helpers
+ * _get_top_k_continuations (sequence part), _get_running_beams_for_next_iteration, _update_finished_beams and
+ * _check_early_stop_heuristic in one launch, one workgroup per batch item.  cur = tokens generated so far (the column
+ * this step fills), L = the most that may be generated, eos = the one [EOS] id; a candidate "hits" iff its token is eos
+ * or cur + 1 >= L.
+ *   running: the nb best candidates by cand_score + hit * -1e9 -> running_out [B, nb, L] (source row of running_in with
+ *     column cur set), running_beam_scores [B, nb], tok [B * nb] (the token to feed), flat_src [B * nb] (b * nb + source
+ *     beam: the K/V-cache rows to continue from).
+ *   finished pool: candidate score cand_score / (cur + 1)^length_penalty, + -1e9 each when (early_stopping == 1 and the
+ *     item's pool is full), when unsat[b] == 0, and when the candidate is not a hit ranked inside the first nb; the nb
+ *     best of (pool, candidates) -> sequences_out [B, nb, L], beam_scores, is_sent_finished (uint8), gen_len (int64,
+ *     tokens of each finished hypothesis) [B, nb].
+ *   unsat [B] (uint8) &= any(running_beam_scores[b, 0] / h^length_penalty > (finished ? min(beam_scores[b]) : -1e9)),
+ *     h = L when early_stopping == 2 ("never") and length_penalty > 0, else cur + 1.
+ *   hits_all [B] (uint8) = every candidate of the item hit.
+ * Every ranking is by score descending, then merged index ascending (pool before candidates).  Rows are gathered, so
+ * the two sequence buffers are ping-pong pairs (in != out); columns 0 .. cur are written.  The divisions are
+ * multiplications by the f32 reciprocal, as torch divides a device tensor by a host scalar.  nb <= 32. */
+int pgca_beam_step(const float* cand_score, const int64_t* cand_index, int32_t B, int32_t nb, int32_t V, int32_t cur,
+                   int32_t L, int64_t eos, float length_penalty, int32_t early_stopping, const int64_t* running_in,
+                   int64_t* running_out, float* running_beam_scores, const int64_t* sequences_in,
+                   int64_t* sequences_out, float* beam_scores, uint8_t* is_sent_finished, int64_t* gen_len,
+                   uint8_t* unsat, int64_t* tok, int64_t* flat_src, uint8_t* hits_all, void* stream);
 
 #ifdef __cplusplus
 }

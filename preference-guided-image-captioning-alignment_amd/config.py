@@ -54,6 +54,22 @@ def select_recompute(config) -> str:
     return mode
 
 
+GENERATE_KEYS = {"max_length": int, "num_beams": int, "temperature": float, "do_sample": bool, "top_p": float,
+                 "repetition_penalty": float, "length_penalty": float}
+
+
+def generate_kwargs(config) -> Dict[str, Any]:
+    """``evaluation.generate_config`` of a ``Config`` or a plain nested dict as keywords of ``CaptionDecoder.generate`` /
+    ``generate_token_ids`` / ``generate_captions`` (the reference's evaluation script reads the same section key by
+    key).  Keys the section does not set are left to ``generate``'s defaults; a missing section is a ``KeyError`` and
+    a key ``generate`` does not know a ``ValueError``."""
+    section = getattr(config, "config", config)["evaluation"]["generate_config"]
+    unknown = sorted(set(section) - set(GENERATE_KEYS))
+    if unknown:
+        raise ValueError(f"evaluation.generate_config: unsupported keys {unknown}; known: {sorted(GENERATE_KEYS)}")
+    return {k: GENERATE_KEYS[k](v) for k, v in section.items()}
+
+
 class Config:
     def __init__(self, config_path: Optional[str] = None) -> None:
         if config_path is None:

@@ -1,5 +1,5 @@
 // Token selection after the LM head (reference model.py:621-678 -> HF generate's logits processors, sampling and
-// beam-candidate ranking): pgca_select_token and pgca_select_beam_candidates.
+// beam-candidate ranking): pgca_select_token(_ex) and pgca_select_beam_candidates(_ex).
 //
 // A row of 50 260 f32 logits (200 KB) does not fit the LDS, and sorting it is what the torch path pays for.  Both kernels
 // instead make several passes over the row (L2 hits after the first): max, sum-exp, then a 4-bit-per-pass radix select
@@ -7,8 +7,10 @@
 // mass for top-p - and finally a prefix scan in token-id order for the draw.  One 1024-thread workgroup serves a row
 // (token kernel) or a batch item's nb rows (beam kernel); wave w owns a contiguous slice of the row and reads it with
 // float4 loads.  Every sum is a fixed-order tree (lane-sequential, wave butterfly, 16 wave totals in order): there are
-// no float atomics, so results are bit-identical from run to run.  The only LDS atomics are integer (seen-id bitmask,
-// candidate slots), whose outcome does not depend on arrival order once the candidates are ranked.
+// no float atomics, so results are bit-identical from run to run.  The only LDS atomics are integer (seen-id and
+// banned-id bitmasks, candidate slots), whose outcome does not depend on arrival order once the candidates are ranked.
+// The _ex entries add a second bitmask plane per row: the ids HF's NoRepeatNGram / MinLength / SuppressTokens
+// processors set to -inf.
 #include "common.h"
 
 #include <math.h>
@@ -39,18 +41,21 @@ __device__ __forceinline__ float okey_inv(unsigned k) {
 }
 
 // One logits row seen through HF's processors: repetition penalty (once per distinct seen id: the ids are a bitmask),
-// then - when warping - the temperature.  For the beam kernel the processors act on log-probabilities: ``shift`` is the
-// row's max and ``shift_log`` the log of its sum-exp, subtracted one after the other as torch's log_softmax does (their
-// sum, rounded once at magnitude ~30, would cost 1e-6); both are 0 for the token kernel.
+// then the bans (-inf whatever the penalty made of the score), then - when warping - the temperature.  For the beam
+// kernel the processors act on log-probabilities: ``shift`` is the row's max and ``shift_log`` the log of its sum-exp,
+// subtracted one after the other as torch's log_softmax does (their sum, rounded once at magnitude ~30, would cost
+// 1e-6); both are 0 for the token kernel.
 struct RowView {
   const float* x;
   const unsigned* seen;  // LDS bitmask over [0, V), or nullptr
+  const unsigned* ban;   // LDS bitmask of the banned ids, or nullptr
   int V, nvec;
   float shift, shift_log, penalty, temperature;
   bool warp;
   __device__ __forceinline__ float score(float xv, int j) const {
     float s = (xv - shift) - shift_log;
     if (seen && ((seen[j >> 5] >> (j & 31)) & 1u)) s = s < 0.f ? s * penalty : s / penalty;
+    if (ban && ((ban[j >> 5] >> (j & 31)) & 1u)) s = -INFINITY;
     if (warp) s = s / temperature;
     return s + 0.0f;  // -0 -> +0: one key per value
   }
@@ -186,6 +191,29 @@ __device__ __forceinline__ void build_seen(unsigned* seen, int words, const long
   __syncthreads();
 }
 
+// bitmask of the ids banned for one row: HF's NoRepeatNGramLogitsProcessor (n > 0: the token that followed every
+// earlier occurrence of the row's last n - 1 ids; n == 1: every seen id; fewer than n - 1 ids: nothing) and a list
+// banned in every row.  Ids outside [0, V) are ignored.
+__device__ __forceinline__ void build_ban(unsigned* ban, int words, const long long* prev, int n_prev, int V, int n,
+                                          const long long* ban_ids, int n_ban) {
+  for (int i = threadIdx.x; i < words; i += SEL_THREADS) ban[i] = 0u;
+  __syncthreads();
+  if (n > 0 && n_prev >= n) {
+    const long long* tail = prev + (n_prev - n + 1);   // the last n - 1 ids (read only when i < n_prev - n + 1)
+    for (int i = threadIdx.x; i < n_prev - n + 1; i += SEL_THREADS) {
+      bool match = true;
+      for (int k = 0; k < n - 1; ++k) match = match && prev[i + k] == tail[k];
+      const long long id = prev[i + n - 1];
+      if (match && id >= 0 && id < V) atomicOr(&ban[id >> 5], 1u << (id & 31));
+    }
+  }
+  for (int i = threadIdx.x; i < n_ban; i += SEL_THREADS) {
+    const long long id = ban_ids[i];
+    if (id >= 0 && id < V) atomicOr(&ban[id >> 5], 1u << (id & 31));
+  }
+  __syncthreads();
+}
+
 // Threshold key of the warpers for one row: a token is kept iff okey(score) >= the returned key.
 //   top-k: strictly below the k-th largest goes (ties with the k-th stay);
 //   top-p: ascending, a class of equal scores goes iff the cumulative probability up to and including it is
@@ -224,7 +252,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_token_kernel(
     const float* __restrict__ logits, int ld, int V, const long long* __restrict__ prev, int ld_prev, int n_prev,
     float penalty, float temperature, int top_k, float top_p, const float* __restrict__ u,
     const unsigned char* __restrict__ done, long long pad_id, long long* __restrict__ next,
-    float* __restrict__ next_logp) {
+    float* __restrict__ next_logp, int ngram, const long long* __restrict__ ban_ids, int n_ban) {
   extern __shared__ unsigned seen_lds[];
   __shared__ SelScratch sm;
   __shared__ int pick;
@@ -251,6 +279,12 @@ __global__ __launch_bounds__(SEL_THREADS) void select_token_kernel(
     build_seen(seen_lds, (V + 31) / 32, prev + (size_t)row * ld_prev, n_prev, V);
     r.seen = seen_lds;
   }
+  r.ban = nullptr;
+  if (ngram > 0 || n_ban > 0) {   // second plane, after the seen plane when there is one
+    unsigned* ban = seen_lds + (r.seen ? (V + 31) / 32 : 0);
+    build_ban(ban, (V + 31) / 32, prev + (size_t)row * ld_prev, n_prev, V, ngram, ban_ids, n_ban);
+    r.ban = ban;
+  }
   // pass 1: raw max (for the log-softmax) and the best processed score (lowest id among equals)
   float mr = -INFINITY;
   unsigned long long best = 0ull;
@@ -266,7 +300,8 @@ __global__ __launch_bounds__(SEL_THREADS) void select_token_kernel(
   for_each(r, [&](int, float xv) { zr += expf(xv - mr); });
   zr = block_sum(zr, sm);
   int chosen = best ? (int)(0xffffffffu - (unsigned)(best & 0xffffffffull)) : 0;   // all-NaN row: id 0
-  if (sample) {
+  // every token banned: the lowest id (``best`` above), nothing to draw from
+  if (sample && (unsigned)(best >> 32) > okey(-INFINITY)) {
     const unsigned key_max = (unsigned)(best >> 32);
     const float m = okey_inv(key_max);
     const unsigned t = warp_threshold(r, key_max, top_k, top_p, sm);
@@ -389,7 +424,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_beam_kernel(
     const float* __restrict__ logits, int ld, int V, int nb, const long long* __restrict__ prev, int ld_prev,
     int n_prev, float penalty, int warp, float temperature, int top_k, float top_p,
     const float* __restrict__ beam_scores, int K, int use_noise, unsigned noise_seed, float* __restrict__ cand_score,
-    long long* __restrict__ cand_index) {
+    long long* __restrict__ cand_index, int ngram, const long long* __restrict__ ban_ids, int n_ban) {
   extern __shared__ unsigned seen_lds[];
   __shared__ SelScratch sm;
   __shared__ float row_max[SEL_MAX_NB], row_logz[SEL_MAX_NB], row_bs[SEL_MAX_NB];
@@ -400,6 +435,8 @@ __global__ __launch_bounds__(SEL_THREADS) void select_beam_kernel(
   const int b = blockIdx.x;
   const int words = (V + 31) / 32;
   const bool pen = penalty != 1.f && n_prev > 0;
+  const bool bans = ngram > 0 || n_ban > 0;
+  unsigned* ban_lds = seen_lds + (pen ? (size_t)nb * words : 0);   // the ban planes follow the seen planes
   auto view = [&](int i) {
     RowView r;
     r.x = logits + (size_t)(b * nb + i) * ld;
@@ -409,6 +446,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_beam_kernel(
     r.temperature = temperature;
     r.warp = warp != 0;
     r.seen = pen ? seen_lds + (size_t)i * words : nullptr;
+    r.ban = bans ? ban_lds + (size_t)i * words : nullptr;
     r.shift = 0.f;
     r.shift_log = 0.f;
     return r;
@@ -417,6 +455,10 @@ __global__ __launch_bounds__(SEL_THREADS) void select_beam_kernel(
   for (int i = 0; i < nb; ++i) {
     RowView r = view(i);
     if (pen) build_seen(seen_lds + (size_t)i * words, words, prev + (size_t)(b * nb + i) * ld_prev, n_prev, V);
+    if (bans) {
+      build_ban(ban_lds + (size_t)i * words, words, prev + (size_t)(b * nb + i) * ld_prev, n_prev, V, ngram, ban_ids,
+                n_ban);
+    }
     float mr = -INFINITY;
     for_each(r, [&](int, float xv) { mr = fmaxf(mr, xv); });
     mr = block_max(mr, sm);
@@ -433,7 +475,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_beam_kernel(
         best = c > best ? c : best;
       });
       best = block_max64(best, sm);
-      thr = warp_threshold(r, (unsigned)(best >> 32), top_k, top_p, sm);
+      if ((unsigned)(best >> 32) > okey(-INFINITY)) thr = warp_threshold(r, (unsigned)(best >> 32), top_k, top_p, sm);
     }
     if (threadIdx.x == 0) {
       row_max[i] = r.shift;
@@ -525,20 +567,69 @@ constexpr size_t SEL_MAX_DYN_LDS = 60 * 1024;
 
 using namespace pgca;
 
+namespace {
+const pgca_select_opts NO_OPTS = {0, 0, nullptr};
+}
+
+extern "C" int pgca_sizeof_select_opts(void) { return (int)sizeof(pgca_select_opts); }
+
+extern "C" int pgca_select_token_ex(const float* logits, int32_t ld, int32_t V, int32_t R, const int64_t* prev,
+                                    int32_t ld_prev, int32_t n_prev, float repetition_penalty, float temperature,
+                                    int32_t top_k, float top_p, const float* u, const uint8_t* done, int64_t pad_id,
+                                    int64_t* next, float* next_logp, const pgca_select_opts* opts, void* stream) {
+  REQUIRE(logits && next && next_logp && R > 0 && V > 0 && ld >= V && (ld % 4) == 0 &&
+              (((uintptr_t)logits & 15) == 0) && n_prev >= 0 && (n_prev == 0 || (prev && ld_prev >= n_prev)) &&
+              repetition_penalty > 0.f && temperature > 0.f && top_k >= 0 && top_p > 0.f && opts &&
+              opts->no_repeat_ngram_size >= 0 && opts->n_ban >= 0 && (opts->n_ban == 0 || opts->ban_ids),
+          "pgca_select_token");
+  const size_t plane = (size_t)((V + 31) / 32) * 4;
+  const size_t lds = ((repetition_penalty != 1.f && n_prev > 0) ? plane : 0) +
+                     ((opts->no_repeat_ngram_size > 0 || opts->n_ban > 0) ? plane : 0);
+  if (lds > SEL_MAX_DYN_LDS) {
+    set_error("pgca_select_token: the seen-id and banned-id bitmasks need more than the 61440 bytes of LDS available");
+    return PGCA_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(select_token_kernel, dim3(R), dim3(SEL_THREADS), lds, (hipStream_t)stream, logits, ld, V,
+                     (const long long*)prev, ld_prev, n_prev, repetition_penalty, temperature, top_k, top_p, u, done,
+                     (long long)pad_id, (long long*)next, next_logp, opts->no_repeat_ngram_size,
+                     (const long long*)opts->ban_ids, opts->n_ban);
+  return check_launch("pgca_select_token");
+}
+
 extern "C" int pgca_select_token(const float* logits, int32_t ld, int32_t V, int32_t R, const int64_t* prev,
                                  int32_t ld_prev, int32_t n_prev, float repetition_penalty, float temperature,
                                  int32_t top_k, float top_p, const float* u, const uint8_t* done, int64_t pad_id,
                                  int64_t* next, float* next_logp, void* stream) {
-  REQUIRE(logits && next && next_logp && R > 0 && V > 0 && ld >= V && (ld % 4) == 0 &&
-              (((uintptr_t)logits & 15) == 0) && n_prev >= 0 && (n_prev == 0 || (prev && ld_prev >= n_prev)) &&
-              repetition_penalty > 0.f && temperature > 0.f && top_k >= 0 && top_p > 0.f,
-          "pgca_select_token");
-  const size_t lds = (repetition_penalty != 1.f && n_prev > 0) ? (size_t)((V + 31) / 32) * 4 : 0;
-  REQUIRE(lds <= SEL_MAX_DYN_LDS, "pgca_select_token");
-  hipLaunchKernelGGL(select_token_kernel, dim3(R), dim3(SEL_THREADS), lds, (hipStream_t)stream, logits, ld, V,
-                     (const long long*)prev, ld_prev, n_prev, repetition_penalty, temperature, top_k, top_p, u, done,
-                     (long long)pad_id, (long long*)next, next_logp);
-  return check_launch("pgca_select_token");
+  return pgca_select_token_ex(logits, ld, V, R, prev, ld_prev, n_prev, repetition_penalty, temperature, top_k, top_p, u,
+                              done, pad_id, next, next_logp, &NO_OPTS, stream);
+}
+
+extern "C" int pgca_select_beam_candidates_ex(const float* logits, int32_t ld, int32_t V, int32_t B, int32_t nb,
+                                              const int64_t* prev, int32_t ld_prev, int32_t n_prev,
+                                              float repetition_penalty, int32_t warp, float temperature, int32_t top_k,
+                                              float top_p, const float* beam_scores, int32_t K, int32_t use_noise,
+                                              uint32_t noise_seed, float* cand_score, int64_t* cand_index,
+                                              const pgca_select_opts* opts, void* stream) {
+  REQUIRE(logits && beam_scores && cand_score && cand_index && B > 0 && nb > 0 && nb <= SEL_MAX_NB && V > 0 &&
+              ld >= V && (ld % 4) == 0 && (((uintptr_t)logits & 15) == 0) && n_prev >= 0 &&
+              (n_prev == 0 || (prev && ld_prev >= n_prev)) && repetition_penalty > 0.f && temperature > 0.f &&
+              top_k >= 0 && top_p > 0.f && K > 0 && K <= 64 && (int64_t)nb * V >= K &&
+              (int64_t)nb * V < (1 << 24) && opts && opts->no_repeat_ngram_size >= 0 && opts->n_ban >= 0 &&
+              (opts->n_ban == 0 || opts->ban_ids),
+          "pgca_select_beam_candidates");
+  const size_t plane = (size_t)nb * ((V + 31) / 32) * 4;
+  const size_t lds = ((repetition_penalty != 1.f && n_prev > 0) ? plane : 0) +
+                     ((opts->no_repeat_ngram_size > 0 || opts->n_ban > 0) ? plane : 0);
+  if (lds > SEL_MAX_DYN_LDS) {
+    set_error("pgca_select_beam_candidates: the seen-id and banned-id bitmasks of nb rows need more than the 61440 "
+              "bytes of LDS available");
+    return PGCA_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(select_beam_kernel, dim3(B), dim3(SEL_THREADS), lds, (hipStream_t)stream, logits, ld, V, nb,
+                     (const long long*)prev, ld_prev, n_prev, repetition_penalty, warp, temperature, top_k, top_p,
+                     beam_scores, K, use_noise, noise_seed, cand_score, (long long*)cand_index,
+                     opts->no_repeat_ngram_size, (const long long*)opts->ban_ids, opts->n_ban);
+  return check_launch("pgca_select_beam_candidates");
 }
 
 extern "C" int pgca_select_beam_candidates(const float* logits, int32_t ld, int32_t V, int32_t B, int32_t nb,
@@ -546,15 +637,7 @@ extern "C" int pgca_select_beam_candidates(const float* logits, int32_t ld, int3
                                            float repetition_penalty, int32_t warp, float temperature, int32_t top_k,
                                            float top_p, const float* beam_scores, int32_t K, int32_t use_noise,
                                            uint32_t noise_seed, float* cand_score, int64_t* cand_index, void* stream) {
-  REQUIRE(logits && beam_scores && cand_score && cand_index && B > 0 && nb > 0 && nb <= SEL_MAX_NB && V > 0 &&
-              ld >= V && (ld % 4) == 0 && (((uintptr_t)logits & 15) == 0) && n_prev >= 0 &&
-              (n_prev == 0 || (prev && ld_prev >= n_prev)) && repetition_penalty > 0.f && temperature > 0.f &&
-              top_k >= 0 && top_p > 0.f && K > 0 && K <= 64 && (int64_t)nb * V >= K && (int64_t)nb * V < (1 << 24),
-          "pgca_select_beam_candidates");
-  const size_t lds = (repetition_penalty != 1.f && n_prev > 0) ? (size_t)nb * ((V + 31) / 32) * 4 : 0;
-  REQUIRE(lds <= SEL_MAX_DYN_LDS, "pgca_select_beam_candidates");
-  hipLaunchKernelGGL(select_beam_kernel, dim3(B), dim3(SEL_THREADS), lds, (hipStream_t)stream, logits, ld, V, nb,
-                     (const long long*)prev, ld_prev, n_prev, repetition_penalty, warp, temperature, top_k, top_p,
-                     beam_scores, K, use_noise, noise_seed, cand_score, (long long*)cand_index);
-  return check_launch("pgca_select_beam_candidates");
+  return pgca_select_beam_candidates_ex(logits, ld, V, B, nb, prev, ld_prev, n_prev, repetition_penalty, warp,
+                                        temperature, top_k, top_p, beam_scores, K, use_noise, noise_seed, cand_score,
+                                        cand_index, &NO_OPTS, stream);
 }

@@ -60,6 +60,11 @@ class SkinnyArgs(C.Structure):
     ]
 
 
+class SelectOpts(C.Structure):
+    """``pgca_select_opts``: the banning processors of the ``_ex`` selection entries."""
+    _fields_ = [("no_repeat_ngram_size", _i32), ("n_ban", _i32), ("ban_ids", _vp)]
+
+
 SKINNY_MAX_M = 64  # include/pgca_hip.h PGCA_SKINNY_MAX_M
 
 # name -> argtypes (return type is always int status unless noted)
@@ -117,10 +122,16 @@ _SIGS = {
     "pgca_select_token": [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _f32, _i32, _f32, _vp, _vp, _i64, _vp, _vp, _vp],
     "pgca_select_beam_candidates": [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _i32, _f32, _i32, _f32, _vp, _i32,
                                     _i32, C.c_uint32, _vp, _vp, _vp],
+    "pgca_select_token_ex": [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _f32, _i32, _f32, _vp, _vp, _i64, _vp, _vp,
+                             C.POINTER(SelectOpts), _vp],
+    "pgca_select_beam_candidates_ex": [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _i32, _f32, _i32, _f32, _vp,
+                                       _i32, _i32, C.c_uint32, _vp, _vp, C.POINTER(SelectOpts), _vp],
+    "pgca_beam_step": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                       _vp, _vp, _vp, _vp, _vp],
 }
 EXPORTS = ["pgca_version", "pgca_last_error", "pgca_sizeof_gemm_args", "pgca_sizeof_skinny_args",
-           "pgca_gemm_skinny_workspace"] + list(_SIGS)
-ABI_VERSION = 305  # include/pgca_hip.h PGCA_ABI_VERSION
+           "pgca_sizeof_select_opts", "pgca_gemm_skinny_workspace"] + list(_SIGS)
+ABI_VERSION = 306  # include/pgca_hip.h PGCA_ABI_VERSION
 
 _lib = None
 
@@ -148,6 +159,10 @@ def load() -> C.CDLL:
     if lib.pgca_sizeof_skinny_args() != C.sizeof(SkinnyArgs):
         raise RuntimeError(f"pgca_skinny_args is {lib.pgca_sizeof_skinny_args()} bytes in {LIB_PATH} but "
                            f"{C.sizeof(SkinnyArgs)} in the binding: stale library, rebuild it")
+    lib.pgca_sizeof_select_opts.restype = C.c_int
+    if lib.pgca_sizeof_select_opts() != C.sizeof(SelectOpts):
+        raise RuntimeError(f"pgca_select_opts is {lib.pgca_sizeof_select_opts()} bytes in {LIB_PATH} but "
+                           f"{C.sizeof(SelectOpts)} in the binding: stale library, rebuild it")
     lib.pgca_gemm_skinny_workspace.restype = C.c_int64
     lib.pgca_gemm_skinny_workspace.argtypes = [_i32, _i32, _i32]
     for name, sig in _SIGS.items():
@@ -403,21 +418,46 @@ def logits_logprob(logits, ld, V, row_map, targets, R, out):
 
 
 # --------------------------------------------------------------------------- token selection (generation)
+def _select_opts(no_repeat_ngram_size, ban_ids):
+    n_ban = 0 if ban_ids is None else int(ban_ids.numel())
+    return SelectOpts(int(no_repeat_ngram_size), n_ban, _p(ban_ids) if n_ban else None)
+
+
 def select_token(logits, V, R, prev, n_prev, repetition_penalty, temperature, top_k, top_p, u, done, pad_id, next_ids,
-                 next_logp):
-    """``logits`` [R, >= V] f32 rows (row stride % 4 == 0), ``prev`` [R, >= n_prev] int64 rows; see pgca_hip.h."""
-    _check(load().pgca_select_token(_p(logits), logits.stride(0), V, R, _p(prev), prev.stride(0) if n_prev else 0, n_prev,
-                                    repetition_penalty, temperature, top_k, top_p, _p(u), _p(done), pad_id, _p(next_ids),
-                                    _p(next_logp), _stream()), "pgca_select_token")
+                 next_logp, no_repeat_ngram_size=0, ban_ids=None):
+    """``logits`` [R, >= V] f32 rows (row stride % 4 == 0), ``prev`` [R, >= n_prev] int64 rows; ``ban_ids``: device
+    int64 ids banned in every row; see pgca_hip.h (pgca_select_token_ex)."""
+    opts = _select_opts(no_repeat_ngram_size, ban_ids)
+    _check(load().pgca_select_token_ex(_p(logits), logits.stride(0), V, R, _p(prev), prev.stride(0) if n_prev else 0,
+                                       n_prev, repetition_penalty, temperature, top_k, top_p, _p(u), _p(done), pad_id,
+                                       _p(next_ids), _p(next_logp), C.byref(opts), _stream()), "pgca_select_token_ex")
 
 
 def select_beam_candidates(logits, V, B, nb, prev, n_prev, repetition_penalty, warp, temperature, top_k, top_p,
-                           beam_scores, K, use_noise, noise_seed, cand_score, cand_index):
-    _check(load().pgca_select_beam_candidates(_p(logits), logits.stride(0), V, B, nb, _p(prev),
-                                              prev.stride(0) if n_prev else 0, n_prev, repetition_penalty, int(warp),
-                                              temperature, top_k, top_p, _p(beam_scores), K, int(use_noise),
-                                              noise_seed & 0xFFFFFFFF, _p(cand_score), _p(cand_index), _stream()),
-           "pgca_select_beam_candidates")
+                           beam_scores, K, use_noise, noise_seed, cand_score, cand_index, no_repeat_ngram_size=0,
+                           ban_ids=None):
+    opts = _select_opts(no_repeat_ngram_size, ban_ids)
+    _check(load().pgca_select_beam_candidates_ex(_p(logits), logits.stride(0), V, B, nb, _p(prev),
+                                                 prev.stride(0) if n_prev else 0, n_prev, repetition_penalty, int(warp),
+                                                 temperature, top_k, top_p, _p(beam_scores), K, int(use_noise),
+                                                 noise_seed & 0xFFFFFFFF, _p(cand_score), _p(cand_index),
+                                                 C.byref(opts), _stream()),
+           "pgca_select_beam_candidates_ex")
+
+
+EARLY_STOPPING = {False: 0, True: 1, "never": 2}
+
+
+def beam_step(cand_score, cand_index, B, nb, V, cur, L, eos, length_penalty, early_stopping, running_in, running_out,
+              running_beam_scores, sequences_in, sequences_out, beam_scores, is_sent_finished, gen_len, unsat, tok,
+              flat_src, hits_all):
+    """One step of HF's beam bookkeeping after the candidates are known; ``early_stopping`` is False, True or
+    "never"; ``is_sent_finished`` / ``unsat`` / ``hits_all`` are bool or uint8 tensors; see pgca_hip.h."""
+    _check(load().pgca_beam_step(_p(cand_score), _p(cand_index), B, nb, V, cur, L, eos, length_penalty,
+                                 EARLY_STOPPING[early_stopping], _p(running_in), _p(running_out),
+                                 _p(running_beam_scores), _p(sequences_in), _p(sequences_out), _p(beam_scores),
+                                 _p(is_sent_finished), _p(gen_len), _p(unsat), _p(tok), _p(flat_src), _p(hits_all),
+                                 _stream()), "pgca_beam_step")
 
 
 def dpo_loss(pol_w, pol_l, ref_w, ref_l, B, beta, label_smoothing, loss, dpol_w=None, dpol_l=None, metrics=None):

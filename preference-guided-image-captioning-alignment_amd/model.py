@@ -210,16 +210,40 @@ class CaptionDecoder:
     EOS_CHECK = 8    # tokens between two "has every sequence finished" host read-backs
 
     @staticmethod
+    def _ngram_banned(ids: torch.Tensor, n: int, V: int) -> Optional[torch.Tensor]:
+        """HF's NoRepeatNGramLogitsProcessor as a mask [R, V]: the token that followed every earlier occurrence of the
+        row's last ``n - 1`` ids (``n == 1``: every seen id); None while a row is shorter than ``n``."""
+        n_prev = ids.shape[1]
+        if n_prev < n:
+            return None
+        win = ids.unfold(1, n, 1)                                # [R, n_prev - n + 1, n]
+        match = (win[:, :, :n - 1] == ids[:, None, n_prev - n + 1:]).all(dim=-1)
+        tok = win[:, :, n - 1]
+        tok = torch.where(match & (tok >= 0) & (tok < V), tok, torch.full_like(tok, V))
+        mask = torch.zeros(ids.shape[0], V + 1, dtype=torch.bool, device=ids.device)
+        return mask.scatter_(1, tok, True)[:, :V]
+
+    @staticmethod
     def _process_scores(scores: torch.Tensor, ids: torch.Tensor, repetition_penalty: float, warp: bool,
-                        temperature: float, top_p: float, top_k: int = 0) -> torch.Tensor:
+                        temperature: float, top_p: float, top_k: int = 0, no_repeat_ngram_size: int = 0,
+                        ban_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """HF's logits processors in HF's order (generation/logits_process.py): RepetitionPenaltyLogitsProcessor, then -
         when sampling - TemperatureLogitsWarper, TopKLogitsWarper (scores below the k-th largest go; 0 = off) and
         TopPLogitsWarper (keeps the smallest set with mass >= top_p, at least one token).  ``scores`` are raw logits for
-        greedy / sampling and log-probabilities for beam search."""
+        greedy / sampling and log-probabilities for beam search.  Between the penalty and the warpers sit HF's banning
+        processors, each of which sets scores to -inf: NoRepeatNGramLogitsProcessor (``no_repeat_ngram_size``) and the
+        ids of ``ban_ids`` (SuppressTokensLogitsProcessor; [EOS] while Min(NewTokens)LengthLogitsProcessor holds)."""
         if repetition_penalty != 1.0 and ids.shape[1]:
             seen = torch.gather(scores, 1, ids)
             seen = torch.where(seen < 0, seen * repetition_penalty, seen / repetition_penalty)
             scores = scores.scatter(1, ids, seen)
+        if no_repeat_ngram_size > 0:
+            banned = CaptionDecoder._ngram_banned(ids, int(no_repeat_ngram_size), scores.shape[-1])
+            if banned is not None:
+                scores = scores.masked_fill(banned, float("-inf"))
+        if ban_ids is not None and ban_ids.numel():
+            ok = ban_ids[(ban_ids >= 0) & (ban_ids < scores.shape[-1])]
+            scores = scores.index_fill(1, ok, float("-inf"))
         if warp:
             if temperature != 1.0:
                 scores = scores / float(temperature)
@@ -239,7 +263,10 @@ class CaptionDecoder:
                  temperature: float = 1.0, do_sample: bool = True, top_p: float = 0.9,
                  repetition_penalty: float = 1.1, pad_token_id: Optional[int] = None,
                  eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
-                 use_cache: bool = True, top_k: int = 0, selection: str = "torch", **kwargs) -> torch.Tensor:
+                 use_cache: bool = True, top_k: int = 0, selection: str = "torch", no_repeat_ngram_size: int = 0,
+                 min_length: int = 0, min_new_tokens: Optional[int] = None, max_new_tokens: Optional[int] = None,
+                 suppress_tokens: Optional[List[int]] = None, length_penalty: float = 1.0, early_stopping=False,
+                 return_scores: bool = False, **kwargs):
         """Reference ``CaptionDecoder.generate`` (model.py:621-678): HF ``generate`` started from the single embedding
         ``vision_projection(vision_features)``.  Same arguments; returns the generated ids ``[B, <= max_length - 1]``
         (int64; HF counts the prefix embedding as one of the ``max_length`` positions, generation/utils.py
@@ -258,7 +285,13 @@ class CaptionDecoder:
         ``top_k`` (0 = off) is HF's TopKLogitsWarper, applied when sampling.  ``selection``: ``"torch"`` (default) runs
         the processors, the draw and the candidate ranking as torch ops; ``"device"`` runs them in the HIP selection
         kernels (``hip.select_token`` / ``hip.select_beam_candidates``): the same ids for greedy and deterministic beam
-        search, the same distributions - from a different random stream - when sampling."""
+        search, the same distributions - from a different random stream - when sampling.
+
+        HF's further controls, honoured by both selection paths: ``no_repeat_ngram_size``, ``suppress_tokens``,
+        ``min_length`` (the prefix is one of its positions, as of ``max_length``) / ``min_new_tokens`` and
+        ``max_new_tokens`` (generated tokens only; each wins over its ``*_length`` twin) for every mode;
+        ``length_penalty`` and ``early_stopping`` (False, True or "never") for beam search.  ``return_scores`` (beam
+        search only) returns ``(ids, scores [B] f32)``: HF's ``sequences_scores``."""
         if kwargs:
             raise TypeError(f"unsupported generation arguments: {sorted(kwargs)}")
         if selection not in ("torch", "device"):
@@ -271,15 +304,32 @@ class CaptionDecoder:
         emb = vision_features.to(dev, F32).contiguous()
         B, nb = emb.shape[0], max(1, int(num_beams))
         L = int(max_length) - 1            # tokens to generate: the prefix embedding occupies one position
+        if max_new_tokens is not None:
+            L = int(max_new_tokens)
         if L < 1:
-            raise ValueError(f"max_length={max_length} leaves no room for a generated token (the prefix counts as one)")
+            raise ValueError(f"max_length={max_length}, max_new_tokens={max_new_tokens} leave no room for a generated "
+                             "token (the prefix counts as one position of max_length)")
+        if isinstance(early_stopping, str):
+            if early_stopping != "never":
+                raise ValueError(f"early_stopping={early_stopping!r}: expected False, True or 'never'")
+        else:
+            early_stopping = bool(early_stopping)
+        if return_scores and nb == 1:
+            raise ValueError("return_scores needs beam search (num_beams > 1); generate_candidates returns the "
+                             "log-probabilities of sampled captions")
+        ngram = max(0, int(no_repeat_ngram_size))
+        bans = self._ban_schedule(L, eos, min_length, min_new_tokens, suppress_tokens)
         pv = eng.prefix_embedding(emb)
         if nb > 1:
-            return self._beam_search(pv, B, nb, L, pad, eos, float(temperature), bool(do_sample), float(top_p),
-                                     float(repetition_penalty), generator, use_cache, top_k, selection == "device")
+            seqs, scores, gen_len = self._beam_search(pv, B, nb, L, pad, eos, float(temperature), bool(do_sample),
+                                                      float(top_p), float(repetition_penalty), generator, use_cache,
+                                                      top_k, selection == "device", ngram, bans,
+                                                      float(length_penalty), early_stopping)
+            ids = seqs[:, 0, :max(1, int(gen_len[:, 0].max()))].contiguous()
+            return (ids, scores[:, 0].contiguous()) if return_scores else ids
         if selection == "device":
             ids_buf, n = self._decode_device(pv, L, pad, eos, float(temperature), bool(do_sample), top_k, float(top_p),
-                                             float(repetition_penalty), generator, use_cache)[:2]
+                                             float(repetition_penalty), generator, use_cache, ngram, bans)[:2]
             return self._trim(ids_buf, n, pad)
         # ---- greedy / sampling (HF _sample): preallocated ids, one EOS read-back every EOS_CHECK tokens
         ids_buf = torch.full((B, L), pad, dtype=I64, device=dev)
@@ -290,7 +340,8 @@ class CaptionDecoder:
             ids = ids_buf[:, :n]
             if not use_cache:
                 logits = eng.next_token_logits(pv, ids)
-            scores = self._process_scores(logits.clone(), ids, repetition_penalty, do_sample, temperature, top_p, top_k)
+            scores = self._process_scores(logits.clone(), ids, repetition_penalty, do_sample, temperature, top_p, top_k,
+                                          ngram, bans(n))
             if do_sample:
                 nxt = torch.multinomial(torch.softmax(scores, dim=-1), 1, generator=generator)[:, 0]
             else:
@@ -305,6 +356,21 @@ class CaptionDecoder:
                 logits = eng.decode_advance(nxt)
         return self._trim(ids_buf, n, pad)
 
+    def _ban_schedule(self, L, eos, min_length=0, min_new_tokens=None, suppress_tokens=None):
+        """step -> device int64 ids banned in every row at that step (or None): ``suppress_tokens`` always, and [EOS]
+        while fewer than the minimum number of tokens exist (HF's MinLength / MinNewTokensLength processors).  Lengths
+        as HF counts them for an ``inputs_embeds`` start (``_prepare_generated_length``): the prefix is one position of
+        ``min_length``; ``min_new_tokens`` counts generated tokens and wins."""
+        min_new = max(int(min_length) - 1, 0) if min_new_tokens is None else max(int(min_new_tokens), 0)
+        if min_new > L:
+            raise ValueError(f"min_length={min_length}, min_new_tokens={min_new_tokens} ask for {min_new} generated "
+                             f"tokens but at most {L} are allowed")
+        sup = sorted({int(t) for t in (suppress_tokens or [])})
+        dev = self._o.device
+        always = torch.tensor(sup, dtype=I64, device=dev) if sup else None
+        early = torch.tensor(sup + [int(eos)], dtype=I64, device=dev) if min_new > 0 else None
+        return lambda step: early if step < min_new else always
+
     @staticmethod
     def _trim(ids_buf, n, pad):
         # columns generated after every sequence had finished are all [PAD]: trimming them equals stopping at once
@@ -313,7 +379,7 @@ class CaptionDecoder:
         return ids_buf[:, :max(1, min(n, last_tok))]
 
     def _decode_device(self, pv, L, pad, eos, temperature, do_sample, top_k, top_p, repetition_penalty, generator,
-                       use_cache=True):
+                       use_cache=True, ngram=0, bans=lambda step: None):
         """The greedy / sampling loop of ``generate`` with one ``hip.select_token`` launch per step in place of the
         torch processors and draw (one uniform per row and step from ``generator``).  Returns (ids_buf [R, L], columns
         filled, logp [R] = sum of the model's own log-probability of every generated token, [EOS] included and [PAD]
@@ -333,7 +399,7 @@ class CaptionDecoder:
                 logits = eng.next_token_logits(pv, ids_buf[:, :n])
             u = torch.rand(R, generator=generator, device=dev) if do_sample else None
             hip.select_token(logits, logits.shape[1], R, ids_buf, n, repetition_penalty, temperature, top_k, top_p, u, done, pad, nxt,
-                             step_lp)
+                             step_lp, ngram, bans(n))
             ids_buf[:, n] = nxt
             logp += step_lp
             lengths += ~done
@@ -346,9 +412,13 @@ class CaptionDecoder:
         return ids_buf, n, logp, lengths
 
     def _beam_search(self, pv, B, nb, L, pad, eos, temperature, do_sample, top_p, repetition_penalty, generator,
-                     use_cache, top_k=0, device_select=False) -> torch.Tensor:
-        """HF ``GenerationMixin._beam_search`` (transformers 5.x, generation/utils.py) for ``length_penalty`` 1.0,
-        ``early_stopping`` False, one returned sequence: state tensors and update rules carry HF's names."""
+                     use_cache, top_k=0, device_select=False, ngram=0, bans=lambda step: None, length_penalty=1.0,
+                     early_stopping=False):
+        """HF ``GenerationMixin._beam_search`` (transformers 5.x, generation/utils.py): state tensors and update rules
+        carry HF's names.  Returns (sequences [B, nb, L] best first, beam_scores [B, nb], gen_len [B, nb] = the tokens
+        of each hypothesis): callers slice what they return.  ``device_select``: the candidates come from
+        ``hip.select_beam_candidates`` and everything after them (steps e, f, g) from ONE ``hip.beam_step`` launch;
+        otherwise both are torch ops."""
         eng, dev = self.engine, self._o.device
         R, K2 = B * nb, 2 * nb                                   # beams_to_keep = 2 * num_beams (one EOS id)
         pvr = pv.repeat_interleave(nb, dim=0)
@@ -359,12 +429,22 @@ class CaptionDecoder:
         beam_scores = torch.full((B, nb), -1e9, device=dev)
         is_sent_finished = torch.zeros(B, nb, dtype=torch.bool, device=dev)
         unsat = torch.ones(B, 1, dtype=torch.bool, device=dev)   # is_early_stop_heuristic_unsatisfied
-        top_num_beam_mask = torch.cat([torch.ones(nb, dtype=torch.bool), torch.zeros(nb, dtype=torch.bool)]).to(dev)
         gen_len = torch.zeros(B, nb, dtype=I64, device=dev)      # tokens of each finished hypothesis (HF: beam_indices)
-        ar = torch.arange(B, device=dev)[:, None]
+        full_stop = early_stopping is True                       # HF: `early_stopping is True`, not truthiness
         cur = 0
-        if device_select and do_sample:                          # one noise seed per step, read back once
-            seeds = torch.randint(0, 2 ** 31 - 1, (L,), generator=generator, device=dev).tolist()
+        if device_select:
+            if do_sample:                                        # one noise seed per step, read back once
+                seeds = torch.randint(0, 2 ** 31 - 1, (L,), generator=generator, device=dev).tolist()
+            # sequence rows are gathered: ping-pong pairs (the kernel never gathers in place)
+            running_next, sequences_next = running_sequences.clone(), sequences.clone()
+            topk_log_probs = torch.empty(B, K2, dtype=F32, device=dev)
+            idx = torch.empty(B, K2, dtype=I64, device=dev)
+            tok = torch.empty(R, dtype=I64, device=dev)
+            flat_src = torch.empty(R, dtype=I64, device=dev)
+            hits_all = torch.zeros(B, dtype=torch.bool, device=dev)
+        else:
+            top_num_beam_mask = torch.cat([torch.ones(nb, dtype=torch.bool), torch.zeros(nb, dtype=torch.bool)]).to(dev)
+            ar = torch.arange(B, device=dev)[:, None]
         logits = eng.decode_begin(pvr, L) if use_cache else None
         while True:
             flat = running_sequences.view(R, L)[:, :cur]
@@ -372,61 +452,75 @@ class CaptionDecoder:
                 logits = eng.next_token_logits(pvr, flat)
             V = logits.shape[1]
             if device_select:                                    # one launch: processors, accumulation, ranking / draw
-                seed = seeds[cur] if do_sample else 0
-                topk_log_probs = torch.empty(B, K2, dtype=F32, device=dev)
-                idx = torch.empty(B, K2, dtype=I64, device=dev)
                 hip.select_beam_candidates(logits, V, B, nb, running_sequences.view(R, L), cur, repetition_penalty,
-                                           do_sample, temperature, top_k, top_p, running_beam_scores.contiguous(), K2,
-                                           do_sample, seed, topk_log_probs, idx)
+                                           do_sample, temperature, top_k, top_p, running_beam_scores, K2,
+                                           do_sample, seeds[cur] if do_sample else 0, topk_log_probs, idx, ngram,
+                                           bans(cur))
+                # one launch: steps e, f, g below, state updated in place but for the two gathered sequence buffers
+                hip.beam_step(topk_log_probs, idx, B, nb, V, cur, L, eos, length_penalty, early_stopping,
+                              running_sequences, running_next, running_beam_scores, sequences, sequences_next,
+                              beam_scores, is_sent_finished, gen_len, unsat, tok, flat_src, hits_all)
+                running_sequences, running_next = running_next, running_sequences
+                sequences, sequences_next = sequences_next, sequences
+                cur += 1
+                hits = hits_all
             else:
                 log_probs = torch.log_softmax(logits.float(), dim=-1)
                 log_probs = self._process_scores(log_probs, flat, repetition_penalty, do_sample, temperature, top_p,
-                                                 top_k)
+                                                 top_k, ngram, bans(cur))
                 acc = (log_probs.view(B, nb, V) + running_beam_scores[:, :, None]).view(B, nb * V)
                 if do_sample:                                    # beam-sample: candidates drawn, then ranked by score
                     idx = torch.multinomial(torch.softmax(acc, dim=-1), num_samples=K2, generator=generator)
                     topk_log_probs = torch.gather(acc, 1, idx)
                 else:
                     topk_log_probs, idx = torch.topk(acc, k=K2)
-            src_beam = idx // V
-            topk_running = running_sequences[ar, src_beam]      # [B, 2nb, L]
-            topk_ids = idx % V
-            topk_running[:, :, cur] = topk_ids
-            hits = (topk_ids == eos) | (cur + 1 >= L)            # EosTokenCriteria | MaxLengthCriteria
-            # e. the num_beams best unfinished candidates keep running
-            run_lp = topk_log_probs + hits.float() * -1.0e9
-            nxt_idx = torch.topk(run_lp, k=nb)[1]
-            running_sequences = topk_running[ar, nxt_idx]
-            running_beam_scores = torch.gather(run_lp, 1, nxt_idx)
-            beam_src = torch.gather(src_beam, 1, nxt_idx)        # the beam each running sequence continues
-            # f. finished pool: only candidates ranked inside the first num_beams may finish
-            just = hits & top_num_beam_mask[None, :]
-            fin_lp = topk_log_probs / float(cur + 1)             # length_penalty 1.0
-            fin_lp = fin_lp + (~unsat).float() * -1.0e9 + (~just).float() * -1.0e9
-            m_seq = torch.cat([sequences, topk_running], dim=1)
-            m_sc = torch.cat([beam_scores, fin_lp], dim=1)
-            m_fin = torch.cat([is_sent_finished, just], dim=1)
-            m_len = torch.cat([gen_len, torch.full((B, K2), cur + 1, dtype=I64, device=dev)], dim=1)
-            keep = torch.topk(m_sc, k=nb)[1]
-            sequences, beam_scores = m_seq[ar, keep], torch.gather(m_sc, 1, keep)
-            is_sent_finished, gen_len = torch.gather(m_fin, 1, keep), torch.gather(m_len, 1, keep)
-            cur += 1
-            # g. stop? (_check_early_stop_heuristic with early_stopping=False, _beam_search_has_unfinished_sequences)
-            best_run = running_beam_scores[:, :1] / float(cur)
-            worst_fin = torch.where(is_sent_finished, beam_scores.min(dim=1, keepdim=True)[0],
-                                    torch.full_like(beam_scores, -1.0e9))
-            unsat = unsat & (best_run > worst_fin).any(dim=-1, keepdim=True)
+                src_beam = idx // V
+                topk_running = running_sequences[ar, src_beam]      # [B, 2nb, L]
+                topk_ids = idx % V
+                topk_running[:, :, cur] = topk_ids
+                hits = (topk_ids == eos) | (cur + 1 >= L)            # EosTokenCriteria | MaxLengthCriteria
+                # e. the num_beams best unfinished candidates keep running
+                run_lp = topk_log_probs + hits.float() * -1.0e9
+                nxt_idx = torch.topk(run_lp, k=nb)[1]
+                running_sequences = topk_running[ar, nxt_idx]
+                running_beam_scores = torch.gather(run_lp, 1, nxt_idx)
+                beam_src = torch.gather(src_beam, 1, nxt_idx)        # the beam each running sequence continues
+                # f. finished pool: only candidates ranked inside the first num_beams may finish
+                just = hits & top_num_beam_mask[None, :]
+                fin_lp = topk_log_probs / float((cur + 1) ** length_penalty)
+                if full_stop:                                        # beams_in_batch_are_full
+                    fin_lp = fin_lp + is_sent_finished.all(dim=-1, keepdim=True).float() * -1.0e9
+                fin_lp = fin_lp + (~unsat).float() * -1.0e9 + (~just).float() * -1.0e9
+                m_seq = torch.cat([sequences, topk_running], dim=1)
+                m_sc = torch.cat([beam_scores, fin_lp], dim=1)
+                m_fin = torch.cat([is_sent_finished, just], dim=1)
+                m_len = torch.cat([gen_len, torch.full((B, K2), cur + 1, dtype=I64, device=dev)], dim=1)
+                keep = torch.topk(m_sc, k=nb)[1]
+                sequences, beam_scores = m_seq[ar, keep], torch.gather(m_sc, 1, keep)
+                is_sent_finished, gen_len = torch.gather(m_fin, 1, keep), torch.gather(m_len, 1, keep)
+                cur += 1
+                # g. stop? (_check_early_stop_heuristic, _beam_search_has_unfinished_sequences)
+                hyp = L if (early_stopping == "never" and length_penalty > 0.0) else cur
+                best_run = running_beam_scores[:, :1] / float(hyp ** length_penalty)
+                worst_fin = torch.where(is_sent_finished, beam_scores.min(dim=1, keepdim=True)[0],
+                                        torch.full_like(beam_scores, -1.0e9))
+                unsat = unsat & (best_run > worst_fin).any(dim=-1, keepdim=True)
+                tok = torch.gather(topk_ids, 1, nxt_idx).view(R)
+                flat_src = (beam_src + ar * nb).view(R)
             # HF reads this flag back every step; here every EOS_CHECK steps: once no batch item can improve, the
             # finished pool is closed to new entries (the -1e9 terms above), so the extra steps change nothing
-            if cur >= L or (cur % self.EOS_CHECK == 0 and not bool(unsat.any() & ~hits.all())):
+            if cur >= L:
                 break
-            tok = torch.gather(topk_ids, 1, nxt_idx).view(R)
+            if cur % self.EOS_CHECK == 0:
+                go_on = unsat.any() & ~hits.all()
+                if full_stop:                                    # exists_open_beam
+                    go_on = go_on & ~is_sent_finished.all()
+                if not bool(go_on):
+                    break
             if use_cache:
-                flat_src = (beam_src + ar * nb).view(R)
                 eng.decode_reorder(flat_src)
                 logits = eng.decode_advance(tok)
-        out_len = max(1, int(gen_len[:, 0].max()))
-        return sequences[:, 0, :out_len].contiguous()
+        return sequences, beam_scores, gen_len
 
 
 class PreferenceGuidedCaptioningModel:
@@ -545,12 +639,14 @@ class PreferenceGuidedCaptioningModel:
     def generate_candidates(self, images: torch.Tensor, num_candidates: int, max_length: int = 50,
                             temperature: float = 1.0, top_p: float = 0.9, top_k: int = 0,
                             repetition_penalty: float = 1.1, generator: Optional[torch.Generator] = None,
-                            use_cache: bool = True):
+                            use_cache: bool = True, no_repeat_ngram_size: int = 0, min_length: int = 0,
+                            suppress_tokens: Optional[List[int]] = None):
         """Best-of-N sampling, the step that turns a Stage-1 model into Stage-2 preference data: ``num_candidates``
         sampled captions per image with the model's own log-probability of each.  Returns ``(ids [B, n, L] int64,
         logp [B, n] f32, lengths [B, n] int64)``: ``logp`` sums the log-softmax of the raw logits over the generated
         tokens, [EOS] included and [PAD] excluded; ``lengths`` counts the same tokens.  Device-side selection;
-        ``use_cache`` as in ``generate``."""
+        ``use_cache``, ``no_repeat_ngram_size``, ``min_length`` and ``suppress_tokens`` as in ``generate`` (they steer
+        the draw; ``logp`` stays the log-softmax of the raw logits)."""
         n = int(num_candidates)
         if n < 1:
             raise ValueError(f"num_candidates={num_candidates}: expected at least 1")
@@ -565,9 +661,11 @@ class PreferenceGuidedCaptioningModel:
             emb = self.vision_encoder(images)["embeddings"]
             B = emb.shape[0]
             pv = dec.engine.prefix_embedding(emb.to(self.device, F32).contiguous()).repeat_interleave(n, dim=0)
+            bans = dec._ban_schedule(L, base + 2, min_length, None, suppress_tokens)
             ids_buf, cols, logp, lengths = dec._decode_device(pv, L, base, base + 2, float(temperature), True,
                                                               max(0, int(top_k)), float(top_p), float(repetition_penalty),
-                                                              generator, use_cache)
+                                                              generator, use_cache, max(0, int(no_repeat_ngram_size)),
+                                                              bans)
             ids = dec._trim(ids_buf, cols, base)
             return ids.reshape(B, n, -1).contiguous(), logp.view(B, n), lengths.view(B, n)
         finally:

@@ -4,11 +4,14 @@ configs/default.yaml:92, measured the reference's way - evaluation/metrics.py:86
 ``generate_captions``-style call divided by the images in the batch).
 
     python tools/gen_latency.py [--runs 20] [--max-length 50] [--selection torch|device] [--out FILE.json]
+        [--no-repeat-ngram-size N] [--min-length N] [--min-new-tokens N] [--max-new-tokens N] [--suppress-tokens ID ...]
+        [--length-penalty P] [--early-stopping false|true|never]
 
 Full-size ViT-B/32 + GPT-2-Medium decoder with seeded random weights (no tokenizer / checkpoints offline: the token
 ids are produced, the string decode is not part of the number), images resident on the device.  Modes: the reference's
 defaults (num_beams 4, do_sample, top_p 0.9, repetition penalty 1.1) and greedy; batch 1 and 32; K/V-cache decode
-(default) and the cache-free recompute for comparison."""
+(default) and the cache-free recompute for comparison.  The generation flags are passed through to ``generate`` as
+given (``--length-penalty`` and ``--early-stopping`` to the beam mode only) and recorded in the result."""
 import argparse
 import json
 import os
@@ -34,7 +37,19 @@ def main():
     ap.add_argument("--no-cache-free", action="store_true")
     ap.add_argument("--selection", choices=("torch", "device"), default="torch",
                     help="token selection after the LM head: torch ops (default) or the HIP selection kernels")
+    ap.add_argument("--no-repeat-ngram-size", type=int, default=None)
+    ap.add_argument("--min-length", type=int, default=None)
+    ap.add_argument("--min-new-tokens", type=int, default=None)
+    ap.add_argument("--max-new-tokens", type=int, default=None)
+    ap.add_argument("--suppress-tokens", type=int, nargs="+", default=None)
+    ap.add_argument("--length-penalty", type=float, default=None)
+    ap.add_argument("--early-stopping", choices=("false", "true", "never"), default=None)
     a = ap.parse_args()
+    extra = {k: getattr(a, k) for k in ("no_repeat_ngram_size", "min_length", "min_new_tokens", "max_new_tokens",
+                                        "suppress_tokens") if getattr(a, k) is not None}
+    beam_extra = {} if a.length_penalty is None else {"length_penalty": a.length_penalty}
+    if a.early_stopping is not None:
+        beam_extra["early_stopping"] = {"false": False, "true": True, "never": "never"}[a.early_stopping]
     from pgca_amd.model import PreferenceGuidedCaptioningModel
     dev = torch.device("cuda:0")
     model = PreferenceGuidedCaptioningModel("openai/clip-vit-base-patch32", "gpt2-medium", 512, temperature=0.5,
@@ -43,7 +58,8 @@ def main():
     # random weights never emit [EOS]: every caption runs to max_length, the worst case for latency
     res = {"model": "CLIP-ViT-B/32 + GPT-2-M decoder, random init", "max_length": a.max_length, "runs": a.runs,
            "definition": "wall time of one batch call / images in the batch (reference evaluation/metrics.py:863-893)",
-           "target_p95_ms": 150.0, "selection": a.selection, "cases": []}
+           "target_p95_ms": 150.0, "selection": a.selection, "generation_arguments": {**extra, **beam_extra},
+           "cases": []}
     modes = [("reference defaults: 4 beams, do_sample, top_p 0.9, repetition 1.1",
               dict(num_beams=4, do_sample=True, top_p=0.9, repetition_penalty=1.1)),
              ("greedy", dict(num_beams=1, do_sample=False, repetition_penalty=1.1))]
@@ -51,6 +67,7 @@ def main():
     for B in (1, 32):
         img = torch.randn(B, 3, 224, 224, device=dev)
         for label, kw in modes:
+            kw = {**kw, **extra, **(beam_extra if kw["num_beams"] > 1 else {})}
             for cache in ((True,) if a.no_cache_free else (True, False)):
                 if not cache and (B == 32 and kw["num_beams"] > 1):
                     continue                      # 128 sequences x 50 recomputed prefixes: only worth one data point
