@@ -129,7 +129,8 @@ int pgca_gemm_plan(const pgca_gemm_args* args);
  * first use - no launch calls getenv:
  *   "gemm_tile"      0 automatic | 128 | 256                          (PGCA_GEMM_TILE)
  *   "gemm_schedule"  -1 automatic | 0 | 6 (see pgca_gemm_plan)         (PGCA_GEMM_RING)
- *   "gemm_group"     1 grouped weight-gradient launch | 0 one by one  (PGCA_GEMM_NO_GROUP=1 -> 0)
+ *   "gemm_group"     1 grouped launches (weight gradients, forward pair) | 0 one by one  (PGCA_GEMM_NO_GROUP=1 -> 0)
+ *   "gemm_pair_order" tile order of a paired launch: 0 problem after problem | 1 alternating by 8-row-tile group
  *   "gemm_stagger"   0..64: start-delay step (x 1024 clocks) of the first wave of workgroups of a many-round
  *                    gemm256s launch, which de-phases the CUs' epilogue store bursts   (PGCA_GEMM_STAGGER)
  * Returns PGCA_ERR_INVALID for an unknown name or value. */
@@ -137,7 +138,14 @@ int pgca_set_option(const char* name, int32_t value);
 /* `count` GEMMs in one launch.  Up to four TN problems with epilogue NONE and an f32 (accumulating) output - the four
  * weight gradients of one GPT-2 block (autograd of Conv1D c_attn / c_proj / c_fc / mlp.c_proj, reference
  * modeling_gpt2.py:203,222-224,229-243 under trainer.py:494,606 loss.backward()) - run as ONE grid with the whole K per
- * tile: no split-K, no atomics.  Anything else falls back to `count` ordinary pgca_gemm_bf16 launches. */
+ * tile: no split-K, no atomics.
+ * TWO NT or two NN problems of the same layout, M, N and K that would each run the phase-staggered 256^2 tile without a
+ * K split, with forward epilogues (NONE .. TANH, GELU_NEW_D) - the same layer of the policy and of the frozen reference
+ * policy (the four forwards of a DPO step, trainer.py:575-628) - run as ONE grid of 2 x tiles workgroups; each problem
+ * keeps its whole pgca_gemm_args (operands,
+ * epilogue, bias, residual, outputs, dropout) and every tile computes exactly what it computes in a launch of its own
+ * (same k order, same epilogue code: bit-identical outputs), while the two part-filled last rounds of 256 workgroups
+ * become one.  Anything else falls back to `count` ordinary pgca_gemm_bf16 launches. */
 int pgca_gemm_bf16_grouped(const pgca_gemm_args* args, int32_t count, void* stream);
 
 /* Skinny product for incremental decoding (generation with a K/V cache: reference models/model.py:657-675 -> HF generate,

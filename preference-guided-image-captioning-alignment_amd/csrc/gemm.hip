@@ -393,6 +393,7 @@ GemmTuning& gemm_tuning() {
     v.schedule = env("PGCA_GEMM_RING", -1);
     v.group = env("PGCA_GEMM_NO_GROUP", 0) ? 0 : 1;
     v.stagger = env("PGCA_GEMM_STAGGER", 0);
+    v.pair_order = 0;
     return v;
   }();
   return t;
@@ -410,6 +411,7 @@ extern "C" int pgca_set_option(const char* name, int32_t value) {
   else if (n == "gemm_schedule" && (value == -1 || value == 0 || value == 6)) t.schedule = value;
   else if (n == "gemm_group" && (value == 0 || value == 1)) t.group = value;
   else if (n == "gemm_stagger" && value >= 0 && value <= 64) t.stagger = value;
+  else if (n == "gemm_pair_order" && (value == 0 || value == 1)) t.pair_order = value;
   else {
     set_error("pgca_set_option: unknown option or value out of range (%s = %d)", name, value);
     return PGCA_ERR_INVALID;
@@ -424,8 +426,8 @@ extern "C" int pgca_gemm_plan(const pgca_gemm_args* args) {
   return plan_variant(*args) * 1000000 + 25600 + splits;
 }
 
-extern "C" int pgca_gemm_bf16(const pgca_gemm_args* args, void* stream) {
-  const pgca_gemm_args& a = *args;
+// Argument checks of pgca_gemm_bf16, shared with the paired launch.
+static int check_gemm_args(const pgca_gemm_args& a) {
   if (!a.A || !a.B || a.M <= 0 || a.N <= 0 || a.K <= 0) {
     set_error("pgca_gemm_bf16: null operand or empty shape (M=%d N=%d K=%d)", a.M, a.N, a.K);
     return PGCA_ERR_INVALID;
@@ -475,6 +477,12 @@ extern "C" int pgca_gemm_bf16(const pgca_gemm_args* args, void* stream) {
     set_error("pgca_gemm_bf16: colsum_part needs the DGELU_NEW / MUL_AUX epilogue, ld_colsum >= N and no split-K");
     return PGCA_ERR_INVALID;
   }
+  return PGCA_OK;
+}
+
+extern "C" int pgca_gemm_bf16(const pgca_gemm_args* args, void* stream) {
+  const pgca_gemm_args& a = *args;
+  if (const int rc = check_gemm_args(a)) return rc;
   const int ncols = a.epilogue == PGCA_EPI_DLOGITS ? a.out_cols : a.N;
   hipStream_t s = (hipStream_t)stream;
   {
@@ -514,6 +522,22 @@ extern "C" int pgca_gemm_bf16_grouped(const pgca_gemm_args* args, int32_t count,
   if (!args || count <= 0) {
     set_error("pgca_gemm_bf16_grouped: no problems");
     return PGCA_ERR_INVALID;
+  }
+  // Two NT or two NN problems of one shape that would each run the phase-staggered 256^2 kernel unsplit: one grid.
+  if (count == 2 && gemm_tuning().group) {
+    const pgca_gemm_args &a = args[0], &b = args[1];
+    int sa = 1, sb = 1;
+    const bool pair = (a.layout == PGCA_NT || a.layout == PGCA_NN) && b.layout == a.layout && a.M == b.M &&
+                      a.N == b.N && a.K == b.K && a.epilogue != PGCA_EPI_DLOGITS && b.epilogue != PGCA_EPI_DLOGITS &&
+                      plan_tile(a, &sa) == 256 && plan_tile(b, &sb) == 256 && sa == 1 && sb == 1 &&
+                      plan_variant(a) == 6 && plan_variant(b) == 6;
+    if (pair) {
+      for (int i = 0; i < 2; ++i) {
+        const int rc = check_gemm_args(args[i]);
+        if (rc) return rc;
+      }
+      return launch_gemm256s_pair(a, b, stream);
+    }
   }
   bool groupable = count <= 4 && gemm_tuning().group;
   for (int i = 0; i < count && groupable; ++i) {

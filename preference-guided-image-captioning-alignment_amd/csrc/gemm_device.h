@@ -1,6 +1,7 @@
-// Device-side building blocks shared by the GEMM translation units (gemm.hip, gemm_phase.hip): operand staging
-// geometry, MFMA fragment readers, the fused epilogues and the LDS-DMA issue helpers.  Everything here has
-// internal linkage; the cross-TU symbols are pgca::launch_gemm256s (gemm_phase.hip) and pgca::gemm_tuning (gemm.hip).
+// Device-side building blocks shared by the GEMM translation units (gemm.hip, gemm_phase.hip, gemm_pair.hip): operand
+// staging geometry, MFMA fragment readers, the fused epilogues and the LDS-DMA issue helpers.  Everything here has
+// internal linkage; the cross-TU symbols are pgca::launch_gemm256s (gemm_phase.hip), pgca::launch_gemm256s_pair
+// (gemm_pair.hip) and pgca::gemm_tuning (gemm.hip).
 #pragma once
 #include <stdlib.h>
 
@@ -9,12 +10,16 @@
 namespace pgca {
 // 256 x 256, 8 waves, phase-staggered wave groups, 4-stage BK=32 ring (gemm_phase.hip).
 int launch_gemm256s(const pgca_gemm_args& a, int ntm, int ntn, int nk_per_split, int nsplit, void* stream);
+// Two NT or two NN problems of one shape (whole K, no split) as ONE grid of that kernel's tiles (gemm_pair.hip).
+int launch_gemm256s_pair(const pgca_gemm_args& a0, const pgca_gemm_args& a1, void* stream);
 
 // Process-wide dispatch knobs (pgca_set_option / environment, read ONCE): nothing on the launch path calls getenv.
 struct GemmTuning {
   int tile;      // 0 = automatic, 128 / 256 = force that kernel family      (PGCA_GEMM_TILE)
   int schedule;  // -1 = automatic, 0 = 2-stage BK=64 loop, 6 = phase-staggered (PGCA_GEMM_RING)
-  int group;     // 1 = the four weight gradients of a block in one grid        (PGCA_GEMM_NO_GROUP inverts)
+  int group;     // 1 = grouped launches: the four weight gradients of a block, the forward pair of two trunks
+                 //                                                              (PGCA_GEMM_NO_GROUP inverts)
+  int pair_order;  // tile order of the paired launch: 0 = problem after problem, 1 = alternating by GROUP_M group
   int stagger;   // start delay step of the first wave of workgroups, in units of 1024 clocks (PGCA_GEMM_STAGGER)
 };
 GemmTuning& gemm_tuning();

@@ -351,6 +351,35 @@ class DecodeState:
     lnf_done: bool = False     # the last step left ln_f(x) in ``gen.y`` (skinny path): the LM head's operand
 
 
+def _drive(steps):
+    """Run a launch generator (``GptTrunk.forward_steps``): it launches everything but its GEMMs itself and yields those
+    as ``(args, kwargs)`` of ``hip.gemm``.  Returns the generator's result."""
+    while True:
+        try:
+            args, kw = next(steps)
+        except StopIteration as e:
+            return e.value
+        hip.gemm(*args, **kw)
+
+
+def _drive_pair(steps0, steps1):
+    """Run two launch generators in lockstep: what each launches itself (LayerNorm, attention) stays per generator, the
+    n-th GEMM of one and the n-th of the other go out as one ``hip.gemm_pair``.  Returns both results."""
+    out = [None, None]
+    while True:
+        g = []
+        for i, steps in enumerate((steps0, steps1)):
+            try:
+                g.append(next(steps))
+            except StopIteration as e:
+                out[i] = e.value
+        if not g:
+            return out
+        if len(g) != 2:
+            raise RuntimeError("paired forward: the two trunks do not have the same sequence of GEMMs")
+        hip.gemm_pair(g[0], g[1])
+
+
 class GptTrunk:
     """GPT-2 blocks + ln_f on an f32 residual stream (HF GPT2Block, modeling_gpt2.py:246-310).
 
@@ -402,7 +431,12 @@ class GptTrunk:
 
     def forward(self, h0: torch.Tensor, mask: Optional[torch.Tensor], Bq: int, S: int, save: bool,
                 drop=None, pack: Optional[RowPack] = None) -> torch.Tensor:
-        """h0 [Bq*S, H] f32 (already including positions) -> residual stream after the last block.
+        return _drive(self.forward_steps(h0, mask, Bq, S, save, drop, pack))
+
+    def forward_steps(self, h0: torch.Tensor, mask: Optional[torch.Tensor], Bq: int, S: int, save: bool,
+                      drop=None, pack: Optional[RowPack] = None):
+        """Launch generator of the forward (``_drive`` runs it; ``_drive_pair`` runs two trunks layer by layer with
+        their GEMMs paired): h0 [Bq*S, H] f32 (already including positions) -> residual stream after the last block.
         ``drop(layer, kind)`` (optional) yields the dropout triple of a site (train mode).
         ``pack``: h0 holds the packed rows [pack.Mp, H] instead (``RowPack``): every kernel runs on those rows only, the
         attention takes the sequence offsets, and the dropout sites hash the padded position of each row."""
@@ -422,7 +456,7 @@ class GptTrunk:
             # a training forward must not overwrite the layer's input (the backward reads it, and under recompute it is
             # the checkpoint); an evaluation forward runs the residual adds in place
             hn = self._buf(f"l{li + 1}.hin", (M, H), F32) if save else None
-            s, hn = self._layer_fwd(li, h, rw, mask, S, drop, save, hn=hn)
+            s, hn = yield from self._layer_steps(li, h, rw, mask, S, drop, save, hn=hn)
             if save:
                 sv[li] = s if self.recompute == "none" else {k: s[k] for k in self._KEPT[self.recompute]}
             h = hn
@@ -446,9 +480,13 @@ class GptTrunk:
             return f"l{li}.{name}"
         return (f"rc{li & 1}." if name in self._WGRAD_OPERANDS else "rc.") + name
 
-    def _layer_fwd(self, li: int, h: torch.Tensor, rw: SimpleNamespace, mask, S: int, drop, save: bool,
-                   hn: Optional[torch.Tensor] = None, hm: Optional[torch.Tensor] = None, proj: bool = True):
-        """Launches of block ``li`` on its input ``h``: the forward's, and the backward's when it rebuilds what a
+    def _layer_fwd(self, *args, **kw):
+        return _drive(self._layer_steps(*args, **kw))
+
+    def _layer_steps(self, li: int, h: torch.Tensor, rw: SimpleNamespace, mask, S: int, drop, save: bool,
+                     hn: Optional[torch.Tensor] = None, hm: Optional[torch.Tensor] = None, proj: bool = True):
+        """Launch generator (every launch but the GEMMs runs here; those are yielded as ``(args, kwargs)`` of
+        ``hip.gemm``).  Launches of block ``li`` on its input ``h``: the forward's, and the backward's when it rebuilds what a
         recompute mode did not keep - the SAME launches on the same operands, so the rebuilt buffers equal the first
         pass bit for bit (every dropout site is a counter hash of the padded position).  ``hm`` given: the attention
         half is skipped (its saved output is ``hm``).  ``proj`` False: stop before ``mlp.c_proj`` (nothing in the
@@ -465,13 +503,13 @@ class GptTrunk:
             ln1, m1, r1 = buf("ln1", (M, H), BF16), buf("m1", (M,), F32), buf("r1", (M,), F32)
             hip.layernorm_fwd(h, M, H, P["ln1w"].w, P["ln1b"].w, a.eps, y_bf16=ln1, mean=m1, rstd=r1)
             qkv = buf("qkv", (M, 3 * H), BF16)
-            hip.gemm(ln1, P["wqkv"].b, M, 3 * H, H, hip.NN, bias=P["bqkv"].w, out_bf16=qkv)
+            yield (ln1, P["wqkv"].b, M, 3 * H, H, hip.NN), dict(bias=P["bqkv"].w, out_bf16=qkv)
             att = buf("att", (M, H), BF16)
             lse = buf("lse", (rw.nseq, a.heads, S), F32)
             hip.attention_fwd(qkv, mask, rw.nseq, S, a.heads, True, att, lse, drop=_dsite(drop, li, KIND_ATTN), cu=rw.cu)
             hm = buf("hm", (M, H), F32) if save else h
-            hip.gemm(att, P["wo"].b, M, H, H, hip.NN, bias=P["bo"].w, residual=h, out_f32=hm,
-                     drop=_dsite(drop, li, KIND_RESID_ATTN), drop_rows=rw.ids)
+            yield (att, P["wo"].b, M, H, H, hip.NN), dict(bias=P["bo"].w, residual=h, out_f32=hm,
+                                                          drop=_dsite(drop, li, KIND_RESID_ATTN), drop_rows=rw.ids)
         s["hm"] = hm
         ln2, m2, r2 = buf("ln2", (M, H), BF16), buf("m2", (M,), F32), buf("r2", (M,), F32)
         hip.layernorm_fwd(hm, M, H, P["ln2w"].w, P["ln2b"].w, a.eps, y_bf16=ln2, mean=m2, rstd=r2)
@@ -480,15 +518,15 @@ class GptTrunk:
         # data-gradient GEMM then only multiplies (EPI_MUL_AUX) instead of evaluating the sigmoid a second time
         pre = buf("pre", (M, I), BF16) if save else None
         s["pre"] = pre
-        hip.gemm(ln2, P["wfc"].b, M, I, H, hip.NN,
-                 epilogue=hip.EPI_GELU_NEW_D if (save and self.GELU_PAIR) else hip.EPI_GELU_NEW,
-                 bias=P["bfc"].w, out_bf16=act, aux_out=pre)
+        yield (ln2, P["wfc"].b, M, I, H, hip.NN), dict(
+            epilogue=hip.EPI_GELU_NEW_D if (save and self.GELU_PAIR) else hip.EPI_GELU_NEW,
+            bias=P["bfc"].w, out_bf16=act, aux_out=pre)
         if not proj:
             return s, None
         if hn is None:
             hn = hm
-        hip.gemm(act, P["wpr"].b, M, H, I, hip.NN, bias=P["bpr"].w, residual=hm, out_f32=hn,
-                 drop=_dsite(drop, li, KIND_RESID_MLP), drop_rows=rw.ids)
+        yield (act, P["wpr"].b, M, H, I, hip.NN), dict(bias=P["bpr"].w, residual=hm, out_f32=hn,
+                                                       drop=_dsite(drop, li, KIND_RESID_MLP), drop_rows=rw.ids)
         return s, hn
 
     def _recompute(self, li: int, sv: dict, rw: SimpleNamespace) -> dict:
@@ -972,11 +1010,20 @@ class CaptionDecoderEngine:
     def hidden(self, emb: torch.Tensor, sb: SeqBatch, save: bool, drop=None, packed: bool = False) -> torch.Tensor:
         """Residual stream after the last block, [Bq*S, H] f32 - or, ``packed``, the rows of ``sb.pack`` only
         ([pack.Mp, H]: the padded positions are never computed).  ``drop(layer, kind)``: train-mode dropout sites."""
-        a = self.arch.gpt
-        H, Bq, S, XH = a.hidden, sb.Bq, sb.S, self.arch.xattn_heads
+        Bq, S = sb.Bq, sb.S
         pack = sb.pack if packed else None
         if packed and pack is None:
             raise ValueError("packed=True needs a SeqBatch prepared with pack=True")
+        h0, keep = self._embed(emb, sb, drop, pack)
+        hL = self.trunk.forward(h0, sb.mask, Bq, S, save, drop, pack=pack)
+        if save:
+            self.saved = dict(hL=hL, **keep)
+        return hL
+
+    def _embed(self, emb: torch.Tensor, sb: SeqBatch, drop, pack: Optional[RowPack]):
+        """Everything before the trunk: the cross-attention term and the embedding kernel.  Returns the trunk's input
+        h0 and what a training forward keeps for the backward."""
+        H, Bq, S, XH = self.arch.gpt.hidden, sb.Bq, sb.S, self.arch.xattn_heads
         rw = _rows(pack, Bq, S)
         M = rw.M
         pf = self._prefix(emb, Bq, drop)
@@ -989,10 +1036,7 @@ class CaptionDecoderEngine:
             hip.embed_fwd(sb.ids, Bq, S, H, self.wte.w, self.wpe.w, h0, attended=self.ob.w, att_stride=0,
                           gamma=self.anw.w, beta=self.anb.w, eps=1e-5, mean=m0, rstd=r0, U=pf["U"], xheads=XH,
                           drop_x=drop(0, KIND_XATTN), drop_e=drop(0, KIND_EMBD), **rw.embed)
-        hL = self.trunk.forward(h0, sb.mask, Bq, S, save, drop, pack=pack)
-        if save:
-            self.saved = dict(sb=sb, m0=m0, r0=r0, hL=hL, drop=drop, pack=pack, **pf)
-        return hL
+        return h0, dict(sb=sb, m0=m0, r0=r0, drop=drop, pack=pack, **pf)
 
     def token_logprobs(self, hL: torch.Tensor, sb: SeqBatch, save: bool, packed: bool = False) -> torch.Tensor:
         """ln_f on the scored rows only, then the fused LM head: tok_lp [Mc] f32."""
@@ -1020,13 +1064,36 @@ class CaptionDecoderEngine:
         """seq_lp [Bq]: 'sum' (components.py:357-362) or 'mean' (model.py:1082-1083).  ``packed`` (default: whenever the
         batch carries a packed layout) runs the trunk on the real tokens' rows only."""
         packed = (sb.pack is not None) if packed is None else bool(packed)
-        hL = self.hidden(emb, sb, save, drop, packed)
+        return self._reduce(self.hidden(emb, sb, save, drop, packed), sb, reduce, save, packed)
+
+    def _reduce(self, hL: torch.Tensor, sb: SeqBatch, reduce: str, save: bool, packed: bool) -> torch.Tensor:
+        """Everything after the trunk: ln_f + LM head on the scored rows, then the per-sequence sum / mean."""
         tok = self.token_logprobs(hL, sb, save, packed)
         out = self._buf("seq_lp", (sb.Bq,), F32)
         hip.seq_reduce(tok, sb.seq_of_row, sb.n_rows, sb.Bq, sb.counts, 1 if reduce == "mean" else 0, out)
         if save:
             self.saved["reduce"] = reduce
         return out
+
+    @staticmethod
+    def sequence_logprobs_pair(pol: "CaptionDecoderEngine", ref: "CaptionDecoderEngine", emb: torch.Tensor,
+                               remb: torch.Tensor, sb: SeqBatch, reduce: str, save: bool, drop, packed: bool):
+        """``pol.sequence_logprobs(emb, sb, reduce, save, drop, packed)`` and ``ref.sequence_logprobs(remb, sb, reduce,
+        False, None, packed)`` on the same rows, with the layers walked ONCE for both trunks: LayerNorm and attention
+        launch per trunk, c_attn / attn c_proj / c_fc / mlp c_proj of the two are one grouped launch each
+        (``hip.gemm_pair``: the two part-filled last rounds of 256 workgroups become one).  Same buffers, same saved
+        activations and bit-identical results; the LM heads (55 k tiles, no tail to fill) stay separate."""
+        pack = sb.pack if packed else None
+        if packed and pack is None:
+            raise ValueError("packed=True needs a SeqBatch prepared with pack=True")
+        rh0, _ = ref._embed(remb, sb, None, pack)
+        h0, keep = pol._embed(emb, sb, drop, pack)
+        hL, rhL = _drive_pair(pol.trunk.forward_steps(h0, sb.mask, sb.Bq, sb.S, save, drop, pack=pack),
+                              ref.trunk.forward_steps(rh0, sb.mask, sb.Bq, sb.S, False, None, pack=pack))
+        if save:
+            pol.saved = dict(hL=hL, **keep)
+        ref_lp = ref._reduce(rhL, sb, reduce, False, packed)
+        return pol._reduce(hL, sb, reduce, save, packed), ref_lp
 
     def logits(self, emb: torch.Tensor, sb: SeqBatch) -> torch.Tensor:
         """Materialised logits [Bq, S, V] f32 for API compatibility (``mode='generation'``)."""

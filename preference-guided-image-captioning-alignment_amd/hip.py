@@ -187,15 +187,16 @@ def _stream():
 
 
 # --------------------------------------------------------------------------- GEMM
-def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, layout: int, *, lda: int = None, ldb: int = None,
-         epilogue: int = EPI_NONE, alpha: float = 1.0, bias: torch.Tensor = None,
-         out_bf16: torch.Tensor = None, ld_out_bf16: int = None, out_f32: torch.Tensor = None, ld_out_f32: int = None,
-         accumulate: bool = False, residual: torch.Tensor = None, ld_res: int = None,
-         aux_out: torch.Tensor = None, aux_in: torch.Tensor = None, ld_aux: int = None,
-         targets: torch.Tensor = None, stat_max: torch.Tensor = None, stat_sum: torch.Tensor = None, stat_ld: int = 0,
-         target_val: torch.Tensor = None, row_lse: torch.Tensor = None, row_scale: torch.Tensor = None,
-         out_cols: int = 0, drop=None, colsum_part: torch.Tensor = None, drop_rows: torch.Tensor = None) -> None:
-    a = GemmArgs()
+def _gemm_args(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, layout: int, *, lda: int = None,
+               ldb: int = None, epilogue: int = EPI_NONE, alpha: float = 1.0, bias: torch.Tensor = None,
+               out_bf16: torch.Tensor = None, ld_out_bf16: int = None, out_f32: torch.Tensor = None,
+               ld_out_f32: int = None, accumulate: bool = False, residual: torch.Tensor = None, ld_res: int = None,
+               aux_out: torch.Tensor = None, aux_in: torch.Tensor = None, ld_aux: int = None,
+               targets: torch.Tensor = None, stat_max: torch.Tensor = None, stat_sum: torch.Tensor = None,
+               stat_ld: int = 0, target_val: torch.Tensor = None, row_lse: torch.Tensor = None,
+               row_scale: torch.Tensor = None, out_cols: int = 0, drop=None, colsum_part: torch.Tensor = None,
+               drop_rows: torch.Tensor = None, into: GemmArgs = None) -> GemmArgs:
+    a = GemmArgs() if into is None else into
     a.A, a.B = A.data_ptr(), B.data_ptr()
     a.M, a.N, a.K = M, N, K
     a.lda = lda if lda is not None else (K if layout != TN else M)
@@ -215,8 +216,14 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, layout: int, 
         a.drop_rows = _p(drop_rows)
     if colsum_part is not None:
         a.colsum_part, a.ld_colsum = colsum_part.data_ptr(), colsum_part.shape[1]
+    return a
+
+
+def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, layout: int, **kw) -> None:
+    """One ``pgca_gemm_bf16`` launch; the keywords are those of ``_gemm_args`` (the fields of ``pgca_gemm_args``)."""
+    a = _gemm_args(A, B, M, N, K, layout, **kw)
     probe = gemm_probe
-    if probe is not None and probe.want(layout, epilogue, load().pgca_gemm_plan(C.byref(a))):
+    if probe is not None and probe.want(layout, a.epilogue, load().pgca_gemm_plan(C.byref(a))):
         # HIP events on the launch stream bracket this one kernel (bench.py roofline measurement)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -225,6 +232,24 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, layout: int, 
         probe.add(e0, e1, 2.0 * M * N * K)
         return
     _check(load().pgca_gemm_bf16(C.byref(a), _stream()), "pgca_gemm_bf16")
+
+
+def gemm_pair(g0, g1) -> None:
+    """Two GEMMs as ONE launch where the library can pair them (two NT or two NN problems of one shape on the
+    phase-staggered 256^2 tile: the same layer of the policy and of the reference trunk), else one launch each -
+    bit-identical outputs either way.  ``g0`` / ``g1``: ``(args, kwargs)`` of the two ``gemm`` calls."""
+    arr = (GemmArgs * 2)()
+    for a, (args, kw) in zip(arr, (g0, g1)):
+        _gemm_args(*args, **kw, into=a)
+    probe = gemm_probe
+    if probe is not None and probe.want(arr[0].layout, arr[0].epilogue, load().pgca_gemm_plan(C.byref(arr[0]))):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _check(load().pgca_gemm_bf16_grouped(arr, 2, _stream()), "pgca_gemm_bf16_grouped")
+        e1.record()
+        probe.add(e0, e1, sum(2.0 * a.M * a.N * a.K for a in arr))
+        return
+    _check(load().pgca_gemm_bf16_grouped(arr, 2, _stream()), "pgca_gemm_bf16_grouped")
 
 
 def gemm_wgrad_group(problems) -> None:

@@ -166,9 +166,15 @@ class DPOStep:
         emb2[B:].copy_(emb)
         ref_lp = None
         packed = self.packed and sb.pack is not None and sb.pack.Mp > 0
+        if not self.reference_free and not self.ref_side_stream and packed:
+            # both trunks see the same packed rows: their layers are walked together and each of the four forward GEMMs
+            # of a layer is ONE grouped launch for the pair, whose part-filled last rounds of workgroups become one
+            # (hip.set_option("gemm_group", 0) launches them one by one again)
+            return CaptionDecoderEngine.sequence_logprobs_pair(self.dec, self.ref.dec, emb2, self._ref_emb2(pooled_bf, B),
+                                                               sb, self.reduce, save, plan.bind(TOWER_DECODER), packed)
         if not self.reference_free:
-            # the frozen reference policy runs on its own HIP stream, concurrently with the policy forward:
-            # the two kernel sequences are independent, so one's store-bound epilogues and tile tails are
+            # ref_side_stream: the frozen reference policy runs on its own HIP stream, concurrently with the policy
+            # forward: the two kernel sequences are independent, so one's store-bound epilogues and tile tails are
             # filled by the other's MFMA main loops
             main = torch.cuda.current_stream()
             if not self.ref_side_stream:
@@ -178,15 +184,20 @@ class DPOStep:
             if self._ref_stream is not main:
                 self._ref_stream.wait_stream(main)
             with torch.cuda.stream(self._ref_stream):
-                remb = self.ref.head.forward(pooled_bf, B, False)
-                remb2 = self.ws.get("dpo.remb2", (2 * B, P), F32)
-                remb2[:B].copy_(remb)
-                remb2[B:].copy_(remb)
-                ref_lp = self.ref.dec.sequence_logprobs(remb2, sb, self.reduce, False, packed=packed)
+                ref_lp = self.ref.dec.sequence_logprobs(self._ref_emb2(pooled_bf, B), sb, self.reduce, False,
+                                                        packed=packed)
         pol = self.dec.sequence_logprobs(emb2, sb, self.reduce, save, plan.bind(TOWER_DECODER), packed=packed)
         if ref_lp is not None and self._ref_stream is not torch.cuda.current_stream():
             torch.cuda.current_stream().wait_stream(self._ref_stream)
         return pol, ref_lp
+
+    def _ref_emb2(self, pooled_bf: torch.Tensor, B: int) -> torch.Tensor:
+        """The reference policy's vision embedding, once per sequence of the (chosen | rejected) batch."""
+        remb = self.ref.head.forward(pooled_bf, B, False)
+        remb2 = self.ws.get("dpo.remb2", (2 * B, self.store.arch.proj_dim), F32)
+        remb2[:B].copy_(remb)
+        remb2[B:].copy_(remb)
+        return remb2
 
     def loss_and_grads(self, images: torch.Tensor, sb: SeqBatch, loss_scale: float = 1.0) -> torch.Tensor:
         """Returns the (unscaled) loss as a 1-element device tensor; gradients of ``loss_scale * loss``
