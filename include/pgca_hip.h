@@ -249,6 +249,17 @@ int pgca_attention_bwd(const void* qkv, const void* out, const void* dout, const
                        const int32_t* key_mask, int32_t B, int32_t S, int32_t heads, int32_t causal,
                        void* dqkv, uint32_t drop_seed, uint32_t drop_threshold, float drop_scale,
                        const int32_t* cu_seqlens, void* stream);
+/* The same arguments, contract and results for 1 <= S <= PGCA_ATTN_SPLIT_MAX_S (GPT-2's 1024 positions; nothing longer is
+ * tested): the work is split by role - one workgroup per (head, sequence, 128-key block) sweeps the query blocks for dK /
+ * dV, one per (head, sequence, 128-query block) sweeps the key blocks for dQ - so a workgroup holds one block's
+ * accumulators whatever S is.  Nothing is summed across workgroups: no atomics, no workspace, bitwise reproducible, and
+ * every element is summed in pgca_attention_bwd's order (bit-identical to it wherever both run).  7 matmuls per
+ * (key, query) pair instead of 5.  Both roles run in one grid. */
+#define PGCA_ATTN_SPLIT_MAX_S 1024
+int pgca_attention_bwd_split(const void* qkv, const void* out, const void* dout, const float* lse,
+                             const int32_t* key_mask, int32_t B, int32_t S, int32_t heads, int32_t causal,
+                             void* dqkv, uint32_t drop_seed, uint32_t drop_threshold, float drop_scale,
+                             const int32_t* cu_seqlens, void* stream);
 
 /* ------------------------------------------------------------------ embeddings */
 /* Caption-decoder input (reference model.py:591-601 + modeling_gpt2.py:571-577):

@@ -77,6 +77,7 @@ VIT_ZOO: Dict[str, VitArch] = {
     "openai/clip-vit-base-patch32": VitArch(768, 12, 12, 3072, 32, 224),
     "openai/clip-vit-base-patch16": VitArch(768, 12, 12, 3072, 16, 224),
     "openai/clip-vit-large-patch14": VitArch(1024, 24, 16, 4096, 14, 224),
+    "openai/clip-vit-large-patch14-336": VitArch(1024, 24, 16, 4096, 14, 336),   # 24 x 24 + 1 = 577 tokens
     # small geometries for parity tests (head_dim stays 64 like every real family)
     "tiny-vit": VitArch(128, 2, 2, 256, 32, 64),
 }

@@ -14,6 +14,9 @@ int attention_fwd_tiled(const void* qkv, const int32_t* key_mask, int B, int S, 
 int attention_bwd_tiled(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_mask,
                         int B, int S, int heads, int causal, void* dqkv, uint32_t drop_seed, uint32_t drop_threshold,
                         float drop_scale, const int32_t* cu, void* stream);
+int attention_bwd_split(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_mask,
+                        int B, int S, int heads, int causal, void* dqkv, uint32_t drop_seed, uint32_t drop_threshold,
+                        float drop_scale, const int32_t* cu, void* stream);
 }  // namespace pgca
 
 extern "C" int pgca_attention_fwd(const void* qkv, const int32_t* key_mask, int32_t B, int32_t S, int32_t heads,
@@ -36,5 +39,21 @@ extern "C" int pgca_attention_bwd(const void* qkv, const void* out, const void* 
     return PGCA_ERR_INVALID;
   }
   return attention_bwd_tiled(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, drop_seed, drop_threshold,
+                             drop_scale, cu_seqlens, stream);
+}
+
+// The same contract on the two-role kernels (a dK/dV role per 128-key block, a dQ role per 128-query block): one block's
+// accumulators per workgroup, so the sequence length is bounded by what is tested, not by registers.
+extern "C" int pgca_attention_bwd_split(const void* qkv, const void* out, const void* dout, const float* lse,
+                                        const int32_t* key_mask, int32_t B, int32_t S, int32_t heads, int32_t causal,
+                                        void* dqkv, uint32_t drop_seed, uint32_t drop_threshold, float drop_scale,
+                                        const int32_t* cu_seqlens, void* stream) {
+  if (!qkv || !out || !dout || !lse || !dqkv || B <= 0 || S <= 0 || S > PGCA_ATTN_SPLIT_MAX_S || heads <= 0 ||
+      B > 65535) {
+    set_error("pgca_attention_bwd_split: bad arguments (B=%d S=%d heads=%d; S must be <= %d, B <= 65535)", B, S, heads,
+              PGCA_ATTN_SPLIT_MAX_S);
+    return PGCA_ERR_INVALID;
+  }
+  return attention_bwd_split(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, drop_seed, drop_threshold,
                              drop_scale, cu_seqlens, stream);
 }

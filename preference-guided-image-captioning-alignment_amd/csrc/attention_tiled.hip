@@ -658,6 +658,361 @@ __global__ __launch_bounds__(TNT, ALIAS ? 4 : 2) void attn_bwd_tiled_kernel(cons
   }
 }
 
+// ------------------------------------------------------------------------------------ backward, split by role
+// No sequence-length ceiling in the structure: the one-pass kernel above holds the dQ accumulators of EVERY query block
+// (NQB <= 4), these two roles hold one block's each.
+//   dK/dV role: one workgroup per (head, sequence, 128-key block).  K and V are staged once, the query blocks are swept
+//               (from kb on when causal) with phase A only; dK^t / dV^t accumulate in MFMA accumulators in ascending
+//               query-block order.  No dS image, no dQ.
+//   dQ role:    one workgroup per (head, sequence, 128-query block).  dO, lse and delta are staged once, the key blocks are
+//               swept (up to qb when causal); S, dP and dS are recomputed, dS crosses LDS as above and phase B adds a
+//               fresh dqt per key block in ascending key-block order.
+// Nothing is summed across workgroups (no atomics, no workspace) and every element sees the one-pass kernel's products
+// in the one-pass kernel's order.  7 matmuls per (key, query) pair instead of 5, for nkb + nqb workgroups per
+// (head, sequence) instead of one.  Both roles use the ALIAS layout (K | V | Q | dO, dS^t over V and Q, 75 KiB) and stay
+// within 128 registers: two workgroups per CU, and one grid can carry both roles.  lse / delta live in LDS for ONE
+// 128-query block at a time, so LDS use does not grow with S.
+
+// rows of one 128-query block: delta[row] = sum_d dO[row, d] O[row, d] from the requested registers (8 lanes per row; the
+// (row, chunk) map is stage_load's), summed in the one-pass kernel's order
+__device__ __forceinline__ void split_delta(const StageRegs& po, const StageRegs& pdo, float* dels, int t) {
+#pragma unroll
+  for (int i = 0; i < 1024 / TNT; ++i) {
+    const int idx = t + TNT * i;
+    const int row = idx >> 3, c = idx & 7;
+    const bf16x8 a = __builtin_bit_cast(bf16x8, po.v[i]);
+    const bf16x8 gg = __builtin_bit_cast(bf16x8, pdo.v[i]);
+    float d = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) d += (float)a[e] * (float)gg[e];
+    d += __shfl_xor(d, 1);
+    d += __shfl_xor(d, 2);
+    d += __shfl_xor(d, 4);
+    if (c == 0) dels[row] = d;
+  }
+}
+
+// One 32-query step of phase A for this wave's 16 keys: S and dP with the key on the lane -> the dropped probabilities
+// and dS of two stacked 16x16 tiles.  lses / dels hold the rows of the CURRENT query block (q0 ..).
+__device__ __forceinline__ void split_pair_step(const unsigned char* Qs, const unsigned char* dOs, const float* lses,
+                                                const float* dels, const bf16x8 (&fk)[2], const bf16x8 (&fv)[2], int s,
+                                                int q0, int S, int Sp, int key, bool kvalid, int causal, unsigned bh,
+                                                const Drop& drop, int lane, float (&pd)[2][4], float (&ds)[2][4]) {
+  const float scale = 0.125f;
+  const int g = lane >> 4;
+  f32x4 sa[2], da[2];
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt) {
+    sa[tt] = da[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      sa[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(Qs, (2 * s + tt) * 16, kk, lane), fk[kk], sa[tt], 0, 0,
+                                                       0);
+      da[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(dOs, (2 * s + tt) * 16, kk, lane), fv[kk], da[tt], 0, 0,
+                                                       0);
+    }
+  }
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt) {
+    const int ql = (2 * s + tt) * 16 + g * 4;
+    const f32x4 l4 = *reinterpret_cast<const f32x4*>(lses + ql);
+    const f32x4 d4 = *reinterpret_cast<const f32x4*>(dels + ql);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int q = q0 + ql + r;
+      const bool ok = kvalid && q < S && (!causal || key <= q);
+      const float pu = ok ? __expf(sa[tt][r] * scale - l4[r]) : 0.f;  // undropped probability
+      const float m = drop.on() ? drop.mul((bh * Sp + q) * Sp + key) : 1.f;
+      ds[tt][r] = pu * (da[tt][r] * m - d4[r]) * scale;               // dP = dP_dropped * m
+      pd[tt][r] = pu * m;                                              // dV uses the dropped probabilities
+    }
+  }
+}
+
+__device__ __forceinline__ void split_dkv_role(unsigned char* smem, const bf16_t* __restrict__ qkv,
+                                               const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO,
+                                               const float* __restrict__ lse_i, const int* __restrict__ kmask, int S,
+                                               int heads, int causal, bf16_t* __restrict__ dqkv, const Drop& drop,
+                                               const int* __restrict__ cu, int Sp, int kb) {
+  unsigned char* Ks = smem;
+  unsigned char* Vs = smem + TILE_QKV;
+  unsigned char* Qs = smem + 2 * TILE_QKV;
+  unsigned char* dOs = smem + 3 * TILE_QKV;
+  float* lses = reinterpret_cast<float*>(smem + 4 * TILE_QKV);  // [128]: the current query block's
+  float* dels = lses + TB;                                      // [128]
+  unsigned char* kms = reinterpret_cast<unsigned char*>(dels + TB);  // [128]
+
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int row0 = cu ? cu[b] : b * Sp;  // packed rows: see the forward
+  if (cu) S = min(S, cu[b + 1] - row0);
+  const int k0 = kb * TB;
+  if (k0 >= S) return;  // block-uniform: a short (or empty) sequence has no such key block
+  const int H = heads * DH, ld = 3 * H;
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int g = lane >> 4, i16 = lane & 15;
+  const bf16_t* base = qkv + (size_t)row0 * ld + h * DH;
+  const bf16_t* obase = O + (size_t)row0 * H + h * DH;
+  const bf16_t* dobase = dO + (size_t)row0 * H + h * DH;
+  bf16_t* dbase_g = dqkv + (size_t)row0 * ld + h * DH;
+  const float* lse_row = lse_i + ((size_t)b * heads + h) * Sp;
+  const unsigned bh = (unsigned)b * heads + h;
+
+  const int nblk = (S + TB - 1) / TB;
+  const int qb0 = causal ? kb : 0;
+  // everything the first pair needs is requested before anything waits (one HBM round trip in front of the first MFMA)
+  {
+    StageRegs pk, pv, pq, pdo, po;
+    stage_load(pk, base + H, ld, k0, S, t);
+    stage_load(pv, base + 2 * H, ld, k0, S, t);
+    stage_load(pq, base, ld, qb0 * TB, S, t);
+    stage_load(pdo, dobase, H, qb0 * TB, S, t);
+    stage_load(po, obase, H, qb0 * TB, S, t);
+    const float plse = (t < TB && qb0 * TB + t < S) ? lse_row[qb0 * TB + t] : 0.f;
+    stage_store(pk, Ks, t);
+    stage_store(pv, Vs, t);
+    stage_store(pq, Qs, t);
+    stage_store(pdo, dOs, t);
+    split_delta(po, pdo, dels, t);
+    if (t < TB) lses[t] = plse;
+  }
+  if (t < TB) kms[t] = (k0 + t < S && (!kmask || kmask[b * Sp + k0 + t] != 0)) ? 1 : 0;
+  const int keyw = k0 + 16 * w;            // this wave's first key
+  const bool has_keys = keyw < S;          // wave-uniform
+  const int key = keyw + i16;
+  f32x4 dvT[4], dkT[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dvT[dt] = dkT[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll 1
+  for (int qb = qb0; qb < nblk; ++qb) {
+    // opaque to the optimizer: otherwise every per-lane value that is linear in q0 (the dropout row bases, the staging
+    // addresses) becomes an induction variable of its own, and the 128-register budget has no room for them
+    int q0 = qb * TB;
+    asm volatile("" : "+s"(q0));
+    // (the barrier that closes the previous block protects Qs / dOs / lses / dels)
+    if (qb != qb0) {  // (the first block came with K and V)
+      int tl = t;
+      asm volatile("" : "+v"(tl));
+      StageRegs pq, pdo, po;
+      stage_load(pq, base, ld, q0, S, tl);
+      stage_load(pdo, dobase, H, q0, S, tl);
+      stage_load(po, obase, H, q0, S, tl);
+      const float plse = (tl < TB && q0 + tl < S) ? lse_row[q0 + tl] : 0.f;
+      stage_store(pq, Qs, tl);
+      stage_store(pdo, dOs, tl);
+      split_delta(po, pdo, dels, tl);
+      if (tl < TB) lses[tl] = plse;
+    }
+    __syncthreads();
+    const bool kvalid = key < S && kms[16 * w + i16];
+    if (has_keys) {
+      bf16x8 fk[2], fv[2];                   // B operands (n = key)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        fk[kk] = frag_rows64(Ks, 16 * w, kk, lane);
+        fv[kk] = frag_rows64(Vs, 16 * w, kk, lane);
+      }
+      const int nqt = min(8, (S - q0 + 15) >> 4);          // 16-query tiles with a real row
+      // on the diagonal block queries below this wave's first key see none of its keys
+      const int mi_lo = (causal && qb == kb) ? w : 0;
+#pragma unroll 1
+      for (int s = 0; s < 4; ++s) {
+        if (2 * s < nqt && 2 * s + 1 >= mi_lo) {
+          float pd[2][4], ds[2][4];
+          split_pair_step(Qs, dOs, lses, dels, fk, fv, s, q0, S, Sp, key, kvalid, causal, bh, drop, lane, pd, ds);
+          const bf16x8 fp = pack_acc(pd[0], pd[1]);
+          const bf16x8 fds = pack_acc(ds[0], ds[1]);
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) {
+            dvT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(dOs, QS, s * 32, dt * 16, lane), fp, dvT[dt], 0,
+                                                              0, 0);
+            dkT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(Qs, QS, s * 32, dt * 16, lane), fds, dkT[dt], 0,
+                                                              0, 0);
+          }
+        }
+      }
+    }
+    __syncthreads();  // Qs / dOs / lses / dels are re-filled by the next block
+  }
+  // ---- dK, dV of this key block: dkT[dt][r] = dK[key = keyw + i16][d = dt*16 + 4g + r]; staged in the wave's own 16
+  // rows of the (now free) Q / dO space
+  unsigned char* mine = Qs + (16 * w) * PS;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    u32x2 pk, pv;
+    pk[0] = pack2(dkT[dt][0], dkT[dt][1]);
+    pk[1] = pack2(dkT[dt][2], dkT[dt][3]);
+    pv[0] = pack2(dvT[dt][0], dvT[dt][1]);
+    pv[1] = pack2(dvT[dt][2], dvT[dt][3]);
+    *reinterpret_cast<u32x2*>(mine + i16 * PS + (dt * 16 + g * 4) * 2) = pk;
+    *reinterpret_cast<u32x2*>(mine + i16 * PS + 128 + (dt * 16 + g * 4) * 2) = pv;
+  }
+  if (has_keys) {
+    const int nv = min(16, S - keyw);
+    store_rows16(mine, PS, dbase_g + H, ld, keyw, nv, lane);
+    store_rows16(mine + 128, PS, dbase_g + 2 * H, ld, keyw, nv, lane);
+  }
+}
+
+__device__ __forceinline__ void split_dq_role(unsigned char* smem, const bf16_t* __restrict__ qkv,
+                                              const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO,
+                                              const float* __restrict__ lse_i, const int* __restrict__ kmask, int S,
+                                              int heads, int causal, bf16_t* __restrict__ dqkv, const Drop& drop,
+                                              const int* __restrict__ cu, int Sp, int qb) {
+  unsigned char* Ks = smem;
+  unsigned char* Vs = smem + TILE_QKV;
+  unsigned char* Qs = smem + 2 * TILE_QKV;
+  unsigned char* dOs = smem + 3 * TILE_QKV;
+  static_assert(TILE_P <= 2 * TILE_QKV, "the dS^t image must fit where V and Q were");
+  unsigned char* dSs = Vs;                                      // dS^t image [128 keys][128 queries] over V and Q
+  float* lses = reinterpret_cast<float*>(smem + 4 * TILE_QKV);  // [128]: this query block's
+  float* dels = lses + TB;                                      // [128]
+  unsigned char* kms = reinterpret_cast<unsigned char*>(dels + TB);  // [128]
+
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int row0 = cu ? cu[b] : b * Sp;  // packed rows: see the forward
+  if (cu) S = min(S, cu[b + 1] - row0);
+  const int q0_ = qb * TB;
+  if (q0_ >= S) return;  // block-uniform: a short (or empty) sequence has no such query block
+  const int H = heads * DH, ld = 3 * H;
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int g = lane >> 4, i16 = lane & 15;
+  const bf16_t* base = qkv + (size_t)row0 * ld + h * DH;
+  const bf16_t* obase = O + (size_t)row0 * H + h * DH;
+  const bf16_t* dobase = dO + (size_t)row0 * H + h * DH;
+  bf16_t* dbase_g = dqkv + (size_t)row0 * ld + h * DH;
+  const unsigned bh = (unsigned)b * heads + h;
+
+  {  // the first pair and the block's row constants, requested together
+    StageRegs pk, pv, pq, pdo, po;
+    stage_load(pk, base + H, ld, 0, S, t);
+    stage_load(pv, base + 2 * H, ld, 0, S, t);
+    stage_load(pq, base, ld, q0_, S, t);
+    stage_load(pdo, dobase, H, q0_, S, t);
+    stage_load(po, obase, H, q0_, S, t);
+    const float plse = (t < TB && q0_ + t < S) ? lse_i[((size_t)b * heads + h) * Sp + q0_ + t] : 0.f;
+    split_delta(po, pdo, dels, t);
+    if (t < TB) lses[t] = plse;
+    stage_store(pk, Ks, t);
+    stage_store(pv, Vs, t);
+    stage_store(pq, Qs, t);
+    stage_store(pdo, dOs, t);  // stays for every key block
+  }
+
+  f32x4 dq[4];
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) dq[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const int nkb = causal ? qb + 1 : (S + TB - 1) / TB;
+  const int nqt = min(8, (S - q0_ + 15) >> 4);  // 16-query tiles with a real row
+  unsigned char* mine = dSs + (16 * w) * PS;   // this wave's own 16 rows of the dS^t image (also its store staging)
+
+#pragma unroll 1
+  for (int kb = 0; kb < nkb; ++kb) {
+    const int k0 = kb * TB;
+    // what depends on the query alone (its 32 dropout row bases per lane) is recomputed per key block instead of being
+    // hoisted into registers that the 128-register budget does not have
+    int q0 = q0_;
+    asm volatile("" : "+s"(q0));
+    // (the barrier that closes the previous key block protects Ks / Vs / Qs / kms)
+    if (kb != 0) {  // V and Q were overwritten by the dS^t image
+      int tl = t;   // (the per-thread row addresses are rebuilt here too)
+      asm volatile("" : "+v"(tl));
+      stage_rows(Ks, base + H, ld, k0, S, tl);
+      stage_rows(Vs, base + 2 * H, ld, k0, S, tl);
+      stage_rows(Qs, base, ld, q0, S, tl);
+    }
+    if (t < TB) kms[t] = (k0 + t < S && (!kmask || kmask[b * Sp + k0 + t] != 0)) ? 1 : 0;
+    __syncthreads();
+    const int keyw = k0 + 16 * w;            // this wave's first key
+    const bool has_keys = keyw < S;          // wave-uniform
+    int ll = lane;   // (so are the per-lane tile offsets)
+    asm volatile("" : "+v"(ll));
+    const int gl = ll >> 4, il = ll & 15;
+    const int key = keyw + il;
+    const bool kvalid = key < S && kms[16 * w + il];
+    const int mi_lo = (causal && qb == kb) ? w : 0;
+    u32x2 dsp[8];  // V / Q are still being read by other waves: held until the barrier
+    if (has_keys) {
+      bf16x8 fk[2], fv[2];
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        fk[kk] = frag_rows64(Ks, 16 * w, kk, ll);
+        fv[kk] = frag_rows64(Vs, 16 * w, kk, ll);
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        float pd[2][4], ds[2][4];
+        if (2 * s < nqt && 2 * s + 1 >= mi_lo) {
+          split_pair_step(Qs, dOs, lses, dels, fk, fv, s, q0, S, Sp, key, kvalid, causal, bh, drop, ll, pd, ds);
+        } else {
+#pragma unroll
+          for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ds[tt][r] = 0.f;
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          dsp[2 * s + tt][0] = pack2(ds[tt][0], ds[tt][1]);
+          dsp[2 * s + tt][1] = pack2(ds[tt][2], ds[tt][3]);
+        }
+      }
+    } else {  // no real key in this wave's rows: the dQ product must read zeros there
+#pragma unroll
+      for (int mi = 0; mi < 8; ++mi) dsp[mi] = (u32x2){0u, 0u};
+    }
+    __syncthreads();  // every wave is done with V and Q: their space takes the dS^t image
+#pragma unroll
+    for (int mi = 0; mi < 8; ++mi) *reinterpret_cast<u32x2*>(mine + il * PS + (mi * 16 + gl * 4) * 2) = dsp[mi];
+    __syncthreads();
+    // ---- phase B: dQ[q][d] += dS[q][key] K[key][d] for this wave's 16 queries of the block
+    if (q0 + 16 * w < S) {
+      int nks = (min(TB, S - k0) + 31) >> 5;
+      if (causal && qb == kb) nks = min(nks, (w >> 1) + 1);
+      f32x4 dqt[4];
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) dqt[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+      for (int ks = 0; ks < nks; ++ks) {
+        const bf16x8 fa = frag_tr(dSs, PS, ks * 32, 16 * w, lane);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+          dqt[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, frag_tr(Ks, QS, ks * 32, nt * 16, lane), dqt[nt], 0, 0, 0);
+      }
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) dq[nt] += dqt[nt];
+    }
+    __syncthreads();  // Ks / Vs / Qs are re-filled by the next key block
+  }
+
+  // ---- dQ of this query block: dq[nt][r] = dQ[q = q0 + 16w + 4g + r][d = nt*16 + i16]
+  const int qw = q0_ + 16 * w;
+  if (qw < S) {  // wave-uniform
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        *reinterpret_cast<bf16_t*>(mine + (g * 4 + r) * PS + (nt * 16 + i16) * 2) = f2bf(dq[nt][r]);
+    store_rows16(mine, PS, dbase_g, ld, qw, min(16, S - qw), lane);
+  }
+}
+
+#define PGCA_SPLIT_PARAMS                                                                                              \
+  const bf16_t *__restrict__ qkv, const bf16_t *__restrict__ O, const bf16_t *__restrict__ dO,                        \
+      const float *__restrict__ lse_i, const int *__restrict__ kmask, int S, int heads, int causal,                    \
+      bf16_t *__restrict__ dqkv, Drop drop, const int *__restrict__ cu, int Sp
+#define PGCA_SPLIT_ARGS qkv, O, dO, lse_i, kmask, S, heads, causal, dqkv, drop, cu, Sp
+
+// Both roles in one grid of 2 * nblk workgroups per (head, sequence); the heaviest first when causal: key block 0 sweeps
+// every query block, the last query block every key block.  (A launch per role was measured and lost at every shape.)
+__global__ __launch_bounds__(TNT, 4) void attn_bwd_split_kernel(PGCA_SPLIT_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int nblk = gridDim.z >> 1;
+  if ((int)blockIdx.z < nblk) split_dkv_role(smem, PGCA_SPLIT_ARGS, blockIdx.z);
+  else split_dq_role(smem, PGCA_SPLIT_ARGS, gridDim.z - 1 - blockIdx.z);
+}
+
 constexpr size_t TFWD_LDS = 2 * TILE_QKV + TB;
 constexpr size_t tbwd_lds(int nqb) { return 4 * TILE_QKV + TILE_P + 2 * (size_t)nqb * TB * sizeof(float) + TB; }
 
@@ -683,6 +1038,22 @@ int launch_bwd(const void* qkv, const void* out, const void* dout, const float* 
 }  // namespace
 
 namespace pgca {
+
+int attention_bwd_split(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_mask,
+                        int B, int S, int heads, int causal, void* dqkv, uint32_t drop_seed, uint32_t drop_threshold,
+                        float drop_scale, const int32_t* cu, void* stream) {
+  static const hipError_t attr = hipFuncSetAttribute((const void*)attn_bwd_split_kernel,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)TBWD_ALIAS_LDS);
+  if (attr != hipSuccess) {
+    set_error("attention (split backward): cannot raise dynamic LDS limit");
+    return PGCA_ERR_LAUNCH;
+  }
+  const int nblk = (S + TB - 1) / TB;
+  hipLaunchKernelGGL(attn_bwd_split_kernel, dim3(heads, B, 2 * nblk), dim3(TNT), TBWD_ALIAS_LDS, (hipStream_t)stream,
+                     (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, key_mask, S, heads, causal,
+                     (bf16_t*)dqkv, Drop{drop_seed, drop_threshold, drop_scale}, cu, S);
+  return check_launch("pgca_attention_bwd_split");
+}
 
 int attention_fwd_tiled(const void* qkv, const int32_t* key_mask, int B, int S, int heads, int causal, void* out,
                         float* lse, uint32_t drop_seed, uint32_t drop_threshold, float drop_scale, const int32_t* cu,

@@ -26,7 +26,15 @@ from .arch import GptArch, ModelArch, VitArch
 from .params import ParamStore, Segment, VOCAB_TILE
 
 F32, BF16, I32, I64 = torch.float32, torch.bfloat16, torch.int32, torch.int64
-ATTN_BWD_MAX_S = 512   # include/pgca_hip.h PGCA_ATTN_MAX_S
+ATTN_BWD_MAX_S = 1024        # include/pgca_hip.h PGCA_ATTN_SPLIT_MAX_S
+ATTN_BWD_ONEPASS_MAX_S = 512  # include/pgca_hip.h PGCA_ATTN_MAX_S
+
+
+def attention_backward(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, drop=None, cu=None):
+    """The attention backward of both towers: the one-pass kernel up to 512 tokens (every dQ block in registers), the
+    two-role split kernels beyond, up to 1024.  ``S`` is the padded length under packed rows."""
+    fn = hip.attention_bwd if S <= ATTN_BWD_ONEPASS_MAX_S else hip.attention_bwd_split
+    fn(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, drop=drop, cu=cu)
 
 
 class Workspace:
@@ -444,8 +452,8 @@ class GptTrunk:
         if S > a.n_pos:
             raise ValueError(f"sequence length {S} exceeds GPT-2's {a.n_pos} learned positions")
         if save and S > ATTN_BWD_MAX_S:
-            raise ValueError(f"training needs sequence length <= {ATTN_BWD_MAX_S} (attention backward keeps the query "
-                             f"gradients of every 128-token block in registers); got {S}")
+            raise ValueError(f"training needs sequence length <= {ATTN_BWD_MAX_S} (the longest the attention backward is "
+                             f"built and tested for); got {S}")
         rw = _rows(pack, Bq, S)
         M = rw.M
         if pack is not None:   # its key mask has the rows of the filler: more (unmasked) sequences of the attention launch
@@ -687,8 +695,8 @@ class GptTrunk:
             hip.gemm(g2_bf, P["wo"].b, M, H, H, hip.NT, out_bf16=datt)
             wgrads.append((s["att"], g2_bf, H, H, M, P["wo"].g))
             dqkv = self._buf("dqkv" + par, (M, 3 * H), BF16)
-            hip.attention_bwd(s["qkv"], s["att"], datt, s["lse"], sv["mask"], rw.nseq, S, a.heads, True, dqkv,
-                              drop=_dsite(drop, li, KIND_ATTN), cu=rw.cu)
+            attention_backward(s["qkv"], s["att"], datt, s["lse"], sv["mask"], rw.nseq, S, a.heads, True, dqkv,
+                               drop=_dsite(drop, li, KIND_ATTN), cu=rw.cu)
             hip.gemm(dqkv, P["wqkv"].b, M, H, 3 * H, hip.NT, out_bf16=dln)
             wgrads.append((s["ln1"], dqkv, H, 3 * H, M, P["wqkv"].g))
             # one launch, whole K per tile: no split-K atomics (gemm256_group_tn_kernel)
@@ -831,7 +839,8 @@ class VisionTower:
         B = pixels.shape[0]
         H, T, G, D = a.hidden, a.tokens, a.grid, a.patch_dim
         if save and T > ATTN_BWD_MAX_S:
-            raise ValueError(f"a trainable vision tower needs <= {ATTN_BWD_MAX_S} tokens per image; got {T}")
+            raise ValueError(f"a trainable vision tower needs <= {ATTN_BWD_MAX_S} tokens per image (the longest the "
+                             f"attention backward is built and tested for); got {T}")
         M = B * T
         Kp = self.patch_k
         cols = ws.get("vit.cols", (B * G * G, Kp), BF16)
@@ -924,7 +933,7 @@ class VisionTower:
             hip.gemm(g2_bf, P["wo"].b, M, H, H, hip.NN, out_bf16=datt)
             hip.gemm(g2_bf, s["att"], H, H, M, hip.TN, lda=H, ldb=H, out_f32=P["wo"].g, accumulate=True)
             _bias_grad(ws, M, H, H, P["bo"].g, x_f32=g2)
-            hip.attention_bwd(s["qkv"], s["att"], datt, s["lse"], None, B, T, a.heads, False, dqkv)
+            attention_backward(s["qkv"], s["att"], datt, s["lse"], None, B, T, a.heads, False, dqkv)
             hip.gemm(dqkv, P["wqkv"].b, M, H, 3 * H, hip.NN, out_bf16=dln)
             hip.gemm(dqkv, s["y1"], 3 * H, H, M, hip.TN, lda=3 * H, ldb=H, out_f32=P["wqkv"].g, accumulate=True)
             _bias_grad(ws, M, 3 * H, 3 * H, P["bqkv"].g, x_bf16=dqkv)

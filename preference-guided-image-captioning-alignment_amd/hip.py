@@ -84,6 +84,8 @@ _SIGS = {
     "pgca_colsum": [_vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "pgca_attention_fwd": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_uint32, C.c_uint32, _f32, _vp, _vp],
     "pgca_attention_bwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, C.c_uint32, C.c_uint32, _f32, _vp, _vp],
+    "pgca_attention_bwd_split": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, C.c_uint32, C.c_uint32, _f32, _vp,
+                                 _vp],
     "pgca_embed_fwd": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp,
                        _vp, _i32, _vp],
     "pgca_embed_bwd": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
@@ -372,6 +374,14 @@ def attention_bwd(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, drop
     _check(load().pgca_attention_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(key_mask), B, S, heads,
                                      1 if causal else 0, _p(dqkv), d[0], d[1], d[2], _p(cu), _stream()),
            "pgca_attention_bwd")
+
+
+def attention_bwd_split(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, drop=None, cu=None):
+    """``attention_bwd`` on the two-role kernels (dK/dV per key block, dQ per query block): S <= 1024, same results."""
+    d = drop or _NODROP
+    _check(load().pgca_attention_bwd_split(_p(qkv), _p(out), _p(dout), _p(lse), _p(key_mask), B, S, heads,
+                                           1 if causal else 0, _p(dqkv), d[0], d[1], d[2], _p(cu), _stream()),
+           "pgca_attention_bwd_split")
 
 
 # --------------------------------------------------------------------------- embeddings / ViT input

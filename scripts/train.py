@@ -47,6 +47,17 @@ class SyntheticPairs(Dataset):
         return {"image": img, "caption_ids": self.ids[i, 0], "caption_mask": self.mask[i, 0]}
 
 
+def synthetic_image_size(configured, tower_image: int, tower_name) -> int:
+    """Side of the synthetic images: the vision tower's input size; an explicit ``data.image_size`` must agree with it
+    (the position table has one row per patch of that size)."""
+    if configured is None:
+        return int(tower_image)
+    if int(configured) != int(tower_image):
+        raise ValueError(f"data.image_size = {configured} does not match the vision tower {tower_name!r}, which takes "
+                         f"{tower_image} x {tower_image} images; remove the key or set it to {tower_image}")
+    return int(configured)
+
+
 def set_random_seeds(seed: int) -> None:
     random.seed(seed)
     np.random.seed(seed)
@@ -99,7 +110,8 @@ def main():
         freeze_text_backbone=mc.get("freeze_text_backbone", False), lora_config=mc.get("lora_config"), seed=seed)
     log.info(f"model: {model.store.num_params() / 1e6:.1f} M parameters on {model.device}")
 
-    S, I = int(cfg.get("data.max_caption_length", 128)), int(cfg.get("data.image_size", 224))
+    S = int(cfg.get("data.max_caption_length", 128))
+    I = synthetic_image_size(cfg.get("data.image_size", None), model.arch.vit.image, mc.get("vision_model"))
     vocab = model.arch.gpt.base_vocab
     n = args.synthetic_samples
 
