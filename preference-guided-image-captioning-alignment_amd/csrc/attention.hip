@@ -1,23 +1,10 @@
 // Fused multi-head self-attention for head_dim 64, forward and backward, on MFMA 16x16x32 bf16: the C-ABI entry points.
 // The kernels are the key-tiled ones of attention_tiled.hip for every sequence length (GPT-2 captions S = 128 / 256,
-// CLIP ViT-B/32 T = 50, ViT-L/14 T = 257); at S <= 128 they run one tile per (batch, head) and measured faster than the
-// round-1 single-tile kernels they replace (forward 87 vs 94 us, backward 238 vs 286 us at 256 sequences x 16 heads,
-// dropout 0.1), mainly because the probabilities never cross LDS.
+// CLIP ViT-B/32 T = 50, ViT-L/14 T = 257); at S <= 128 they run one tile per (batch, head), and the probabilities never
+// cross LDS.
 #include "common.h"
 
 using namespace pgca;
-
-namespace pgca {
-int attention_fwd_tiled(const void* qkv, const int32_t* key_mask, int B, int S, int heads, int causal, void* out,
-                        float* lse, uint32_t drop_seed, uint32_t drop_threshold, float drop_scale, const int32_t* cu,
-                        void* stream);
-int attention_bwd_tiled(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_mask,
-                        int B, int S, int heads, int causal, void* dqkv, uint32_t drop_seed, uint32_t drop_threshold,
-                        float drop_scale, const int32_t* cu, void* stream);
-int attention_bwd_split(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_mask,
-                        int B, int S, int heads, int causal, void* dqkv, uint32_t drop_seed, uint32_t drop_threshold,
-                        float drop_scale, const int32_t* cu, void* stream);
-}  // namespace pgca
 
 extern "C" int pgca_attention_fwd(const void* qkv, const int32_t* key_mask, int32_t B, int32_t S, int32_t heads,
                                   int32_t causal, void* out, float* lse, uint32_t drop_seed, uint32_t drop_threshold,
@@ -38,8 +25,9 @@ extern "C" int pgca_attention_bwd(const void* qkv, const void* out, const void* 
     set_error("pgca_attention_bwd: bad arguments (B=%d S=%d heads=%d; S must be <= %d)", B, S, heads, PGCA_ATTN_MAX_S);
     return PGCA_ERR_INVALID;
   }
-  return attention_bwd_tiled(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, drop_seed, drop_threshold,
-                             drop_scale, cu_seqlens, stream);
+  return attention_bwd_tiled({(const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, key_mask, B, S, heads,
+                              causal, (bf16_t*)dqkv, Drop{drop_seed, drop_threshold, drop_scale}, cu_seqlens, S,
+                              (hipStream_t)stream});
 }
 
 // The same contract on the two-role kernels (a dK/dV role per 128-key block, a dQ role per 128-query block): one block's
@@ -54,6 +42,7 @@ extern "C" int pgca_attention_bwd_split(const void* qkv, const void* out, const 
               PGCA_ATTN_SPLIT_MAX_S);
     return PGCA_ERR_INVALID;
   }
-  return attention_bwd_split(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, drop_seed, drop_threshold,
-                             drop_scale, cu_seqlens, stream);
+  return attention_bwd_split({(const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, key_mask, B, S, heads,
+                              causal, (bf16_t*)dqkv, Drop{drop_seed, drop_threshold, drop_scale}, cu_seqlens, S,
+                              (hipStream_t)stream});
 }

@@ -14,7 +14,10 @@
 // Backward: one workgroup per (head, batch) sweeps (key block, query block) pairs.  S and dP are computed with the KEY
 // on the lane, so P and dS accumulators feed dV^t += dO^t P and dK^t += Q^t dS directly as B operands; only dS crosses
 // LDS (once, transposed, 8-byte stores) for dQ += dS K, whose accumulators stay in registers for every query block
-// (template NQB): no atomics, nothing summed across workgroups, bitwise reproducible.
+// (template NQB <= 4, S <= 512): no atomics, nothing summed across workgroups, bitwise reproducible.
+// Backward, split by role (S <= 1024): a dK/dV workgroup per 128-key block sweeps the query blocks, a dQ workgroup per
+// 128-query block sweeps the key blocks, each holding ONE block's accumulators.  Both are built from the one-pass
+// kernel's pieces, so every element sees the same products in the same order: the two entries agree bit for bit.
 #include "common.h"
 
 using namespace pgca;
@@ -382,62 +385,59 @@ __global__ __launch_bounds__(FNT, 4) void attn_fwd_one_kernel(const bf16_t* __re
   }
 }
 
-// ------------------------------------------------------------------------------------ backward
-// ALIAS (one-block sequences only): the dS^t image lives where V and Q were - both are dead once phase A is over - so
-// a workgroup needs 75 KiB of LDS instead of 109 and two of them share a CU (registers capped at 128 for that).
+// ------------------------------------------------------------------------------------ backward: the shared pieces
+// What a backward workgroup knows about its (head, sequence): the LDS carve-up K | V | Q | dO | [dS^t] | lse | delta | kms,
+// the clamped length, the head's global bases and the thread indices.  ALIAS (one (key, query) pair at a time only): the
+// dS^t image lives where V and Q were - both are dead once phase A is over - so a workgroup needs 75 KiB of LDS instead
+// of 109 and two of them share a CU (registers capped at 128 for that).
+struct BwdBlock {
+  unsigned char *Ks, *Vs, *Qs, *dOs;  // [128][64] bf16 images
+  unsigned char* dSs;                 // dS^t image [128 keys][128 queries]
+  unsigned char* mine;                // this wave's own 16 rows of the dS^t image (also its store staging)
+  float *lses, *dels;                 // [NQB * 128] each
+  unsigned char* kms;                 // [128]
+  const bf16_t *base, *obase, *dobase;
+  bf16_t* dbase_g;
+  const float* lse_row;
+  int S, H, ld, b, t, lane, w, g, i16;
+  unsigned bh;
+};
 template <int NQB, bool ALIAS>
-__global__ __launch_bounds__(TNT, ALIAS ? 4 : 2) void attn_bwd_tiled_kernel(const bf16_t* __restrict__ qkv,
-                                                                const bf16_t* __restrict__ O,
-                                                                const bf16_t* __restrict__ dO,
-                                                                const float* __restrict__ lse_i,
-                                                                const int* __restrict__ kmask, int S, int heads,
-                                                                int causal, bf16_t* __restrict__ dqkv, Drop drop,
-                                                                const int* __restrict__ cu, int Sp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* Ks = smem;
-  unsigned char* Vs = smem + TILE_QKV;
-  unsigned char* Qs = smem + 2 * TILE_QKV;
-  unsigned char* dOs = smem + 3 * TILE_QKV;
-  static_assert(!ALIAS || (NQB == 1 && TILE_P <= 2 * TILE_QKV), "aliasing needs a single (key, query) pair");
-  unsigned char* dSs = ALIAS ? Vs : smem + 4 * TILE_QKV;           // dS^t image [128 keys][128 queries]
-  float* lses = reinterpret_cast<float*>(smem + 4 * TILE_QKV + (ALIAS ? 0 : TILE_P));  // [NQB * 128]
-  float* dels = lses + NQB * TB;                                   // [NQB * 128]
-  unsigned char* kms = reinterpret_cast<unsigned char*>(dels + NQB * TB);  // [128]
-
-  const int b = blockIdx.y;
-  const int row0 = cu ? cu[b] : b * Sp;  // packed rows: see the forward
-  if (cu) S = min(S, cu[b + 1] - row0);
-  if (S <= 0) return;
-  const int H = heads * DH, ld = 3 * H;
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int g = lane >> 4, i16 = lane & 15;
-
-  // A workgroup's memory latency is hidden by at most one other workgroup on its CU (none when S > 128): the first
-  // (key block, query block) pair - K, V, Q, dO tiles - is REQUESTED together with the row constants' inputs (O rows for
-  // delta, lse) into registers and stored to LDS afterwards: one HBM round trip in front of the first MFMA instead of
-  // three.  With packed sequences (mean length 72 of 128) most workgroups have exactly one pair.
-  constexpr int NLSE = (NQB * TB + TNT - 1) / TNT;
+__device__ __forceinline__ BwdBlock bwd_block(unsigned char* smem, const AttnBwd& a) {
+  static_assert(!ALIAS || (NQB == 1 && TILE_P <= 2 * TILE_QKV), "the dS^t image must fit where V and Q were");
+  BwdBlock c;
+  c.Ks = smem;
+  c.Vs = smem + TILE_QKV;
+  c.Qs = smem + 2 * TILE_QKV;
+  c.dOs = smem + 3 * TILE_QKV;
+  c.dSs = ALIAS ? c.Vs : smem + 4 * TILE_QKV;
+  c.lses = reinterpret_cast<float*>(smem + 4 * TILE_QKV + (ALIAS ? 0 : TILE_P));
+  c.dels = c.lses + NQB * TB;
+  c.kms = reinterpret_cast<unsigned char*>(c.dels + NQB * TB);
   const int h = blockIdx.x;
-  const bf16_t* base = qkv + (size_t)row0 * ld + h * DH;
-  const bf16_t* obase = O + (size_t)row0 * H + h * DH;
-  const bf16_t* dobase = dO + (size_t)row0 * H + h * DH;
-  bf16_t* dbase_g = dqkv + (size_t)row0 * ld + h * DH;
-  StageRegs pk, pv, pq, pdo, po;
-  float plse[NLSE];
-  stage_load(pk, base + H, ld, 0, S, t);
-  stage_load(pv, base + 2 * H, ld, 0, S, t);
-  stage_load(pq, base, ld, 0, S, t);
-  stage_load(pdo, dobase, H, 0, S, t);
-  stage_load(po, obase, H, 0, S, t);
-#pragma unroll
-  for (int j = 0; j < NLSE; ++j) {
-    const int i = t + TNT * j;
-    plse[j] = i < S ? lse_i[((size_t)b * heads + h) * Sp + i] : 0.f;
-  }
+  c.b = blockIdx.y;
+  const int row0 = a.cu ? a.cu[c.b] : c.b * a.Sp;  // packed rows: see the forward
+  c.S = a.cu ? min(a.S, a.cu[c.b + 1] - row0) : a.S;
+  c.H = a.heads * DH;
+  c.ld = 3 * c.H;
+  c.t = threadIdx.x;
+  c.lane = c.t & 63;
+  c.w = __builtin_amdgcn_readfirstlane(c.t >> 6);
+  c.g = c.lane >> 4;
+  c.i16 = c.lane & 15;
+  c.mine = c.dSs + (16 * c.w) * PS;
+  c.base = a.qkv + (size_t)row0 * c.ld + h * DH;
+  c.obase = a.O + (size_t)row0 * c.H + h * DH;
+  c.dobase = a.dO + (size_t)row0 * c.H + h * DH;
+  c.dbase_g = a.dqkv + (size_t)row0 * c.ld + h * DH;
+  c.lse_row = a.lse + ((size_t)c.b * a.heads + h) * a.Sp;
+  c.bh = (unsigned)c.b * a.heads + h;
+  return c;
+}
 
-  // row constants of every query: lse and delta[q] = sum_d dO[q,d] O[q,d] (8 lanes per row).  Rows of the first query
-  // block come from the requested registers (stage_load's (row, chunk) map is this loop's), later blocks from memory.
+// rows of one 128-query block: delta[row] = sum_d dO[row, d] O[row, d] from the requested registers (8 lanes per row; the
+// (row, chunk) map is stage_load's)
+__device__ __forceinline__ void delta_rows(const StageRegs& po, const StageRegs& pdo, float* dels, int t) {
 #pragma unroll
   for (int i = 0; i < 1024 / TNT; ++i) {
     const int idx = t + TNT * i;
@@ -451,253 +451,71 @@ __global__ __launch_bounds__(TNT, ALIAS ? 4 : 2) void attn_bwd_tiled_kernel(cons
     d += __shfl_xor(d, 2);
     d += __shfl_xor(d, 4);
     if (c == 0) dels[row] = d;
-  }
-  for (int idx = t + 1024; idx < NQB * TB * 8; idx += TNT) {
-    const int row = idx >> 3, c = idx & 7;
-    float d = 0.f;
-    if (row < S) {
-      const bf16x8 a = *reinterpret_cast<const bf16x8*>(obase + (size_t)row * H + c * 8);
-      const bf16x8 gg = *reinterpret_cast<const bf16x8*>(dobase + (size_t)row * H + c * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) d += (float)a[e] * (float)gg[e];
-    }
-    d += __shfl_xor(d, 1);
-    d += __shfl_xor(d, 2);
-    d += __shfl_xor(d, 4);
-    if (c == 0) dels[row] = d;
-  }
-#pragma unroll
-  for (int j = 0; j < NLSE; ++j)
-    if (t + TNT * j < NQB * TB) lses[t + TNT * j] = plse[j];
-
-  f32x4 dq[NQB][4];
-#pragma unroll
-  for (int qb = 0; qb < NQB; ++qb)
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) dq[qb][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const float scale = 0.125f;
-  const int nblk = NQB == 1 ? 1 : (S + TB - 1) / TB;  // key blocks == query blocks (<= NQB; S > 0 here)
-  unsigned char* mine = dSs + (16 * w) * PS;  // this wave's own 16 rows of the dS^t image (also its store staging)
-
-  for (int kb = 0; kb < nblk; ++kb) {
-    const int k0 = kb * TB;
-    // (the barrier that closes the previous pair protects Ks / Vs / kms)
-    if (kb == 0) {   // requested at the top; the first query block (0 in both mask modes) comes with them
-      stage_store(pk, Ks, t);
-      stage_store(pv, Vs, t);
-      stage_store(pq, Qs, t);
-      stage_store(pdo, dOs, t);
-    } else {
-      stage_rows(Ks, base + H, ld, k0, S, t);
-      stage_rows(Vs, base + 2 * H, ld, k0, S, t);
-    }
-    if (t < TB) kms[t] = (k0 + t < S && (!kmask || kmask[b * Sp + k0 + t] != 0)) ? 1 : 0;
-    __syncthreads();
-    const int keyw = k0 + 16 * w;            // this wave's first key
-    const bool has_keys = keyw < S;          // wave-uniform
-    const int key = keyw + i16;
-    bf16x8 fk[2], fv[2];                     // B operands (n = key), loop-invariant over the query blocks
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      fk[kk] = frag_rows64(Ks, 16 * w, kk, lane);
-      fv[kk] = frag_rows64(Vs, 16 * w, kk, lane);
-    }
-    const bool kvalid = key < S && kms[16 * w + i16];
-    f32x4 dvT[4], dkT[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) dvT[dt] = dkT[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    // runtime loop (one copy of the body); only the dQ accumulators are indexed statically, at the end of the pair
-#pragma unroll 1
-    for (int qb = causal ? kb : 0; qb < nblk; ++qb) {
-      {
-        const int q0 = qb * TB;
-        if (kb != 0 || qb != 0) {   // (pair (0, 0) was staged with the key block)
-          stage_rows(Qs, base, ld, q0, S, t);
-          stage_rows(dOs, dobase, H, q0, S, t);
-          __syncthreads();
-        }
-        // ---- phase A: S, dP (key on the lane) -> P, dS -> dV^t, dK^t; dS^t to LDS
-        const int nqt = min(8, (S - q0 + 15) >> 4);          // 16-query tiles with a real row
-        // on the diagonal block queries below this wave's first key see none of its keys
-        const int mi_lo = (causal && qb == kb) ? w : 0;
-        u32x2 dsp[ALIAS ? 8 : 1];
-        auto phase_a = [&](const int s) {
-            float pd[2][4], ds[2][4];
-            if (2 * s < nqt && 2 * s + 1 >= mi_lo) {
-              f32x4 sa[2], da[2];
-#pragma unroll
-              for (int tt = 0; tt < 2; ++tt) {
-                sa[tt] = da[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                  sa[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(Qs, (2 * s + tt) * 16, kk, lane), fk[kk],
-                                                                   sa[tt], 0, 0, 0);
-                  da[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(dOs, (2 * s + tt) * 16, kk, lane), fv[kk],
-                                                                   da[tt], 0, 0, 0);
-                }
-              }
-#pragma unroll
-              for (int tt = 0; tt < 2; ++tt) {
-                const int ql = (2 * s + tt) * 16 + g * 4;
-                const f32x4 l4 = *reinterpret_cast<const f32x4*>(lses + q0 + ql);
-                const f32x4 d4 = *reinterpret_cast<const f32x4*>(dels + q0 + ql);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                  const int q = q0 + ql + r;
-                  const bool ok = kvalid && q < S && (!causal || key <= q);
-                  const float pu = ok ? __expf(sa[tt][r] * scale - l4[r]) : 0.f;  // undropped probability
-                  // (the key runs along the lanes here, so each element has its own pair hash)
-                  const float m = drop.on() ? drop.mul((((unsigned)b * heads + h) * Sp + q) * Sp + key) : 1.f;
-                  ds[tt][r] = pu * (da[tt][r] * m - d4[r]) * scale;               // dP = dP_dropped * m
-                  pd[tt][r] = pu * m;                                              // dV uses the dropped probabilities
-                }
-              }
-              const bf16x8 fp = pack_acc(pd[0], pd[1]);
-              const bf16x8 fds = pack_acc(ds[0], ds[1]);
-#pragma unroll
-              for (int dt = 0; dt < 4; ++dt) {
-                dvT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(dOs, QS, s * 32, dt * 16, lane), fp, dvT[dt],
-                                                                  0, 0, 0);
-                dkT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(Qs, QS, s * 32, dt * 16, lane), fds, dkT[dt],
-                                                                  0, 0, 0);
-              }
-            } else {
-#pragma unroll
-              for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ds[tt][r] = 0.f;
-            }
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) {
-              u32x2 pk;
-              pk[0] = pack2(ds[tt][0], ds[tt][1]);
-              pk[1] = pack2(ds[tt][2], ds[tt][3]);
-              if constexpr (ALIAS) dsp[2 * s + tt] = pk;   // V / Q are still being read: held until the barrier
-              else *reinterpret_cast<u32x2*>(mine + i16 * PS + ((2 * s + tt) * 16 + g * 4) * 2) = pk;
-            }
-        };
-        if (has_keys) {
-          if constexpr (ALIAS) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) phase_a(s);
-          } else {
-#pragma unroll 1
-            for (int s = 0; s < 4; ++s) phase_a(s);
-          }
-        } else {  // no real key in this wave's rows: the dQ product must read zeros there
-#pragma unroll
-          for (int mi = 0; mi < 8; ++mi) {
-            if constexpr (ALIAS) dsp[mi] = (u32x2){0u, 0u};
-            else *reinterpret_cast<u32x2*>(mine + i16 * PS + (mi * 16 + g * 4) * 2) = (u32x2){0u, 0u};
-          }
-        }
-        if constexpr (ALIAS) {
-          __syncthreads();  // every wave is done with V and Q: their space takes the dS^t image
-#pragma unroll
-          for (int mi = 0; mi < 8; ++mi)
-            *reinterpret_cast<u32x2*>(mine + i16 * PS + (mi * 16 + g * 4) * 2) = dsp[mi];
-        }
-        __syncthreads();
-        // ---- phase B: dQ[q][d] += dS[q][key] K[key][d] for this wave's 16 queries of the block
-        if (q0 + 16 * w < S) {
-          int nks = (min(TB, S - k0) + 31) >> 5;
-          if (causal && qb == kb) nks = min(nks, (w >> 1) + 1);
-          f32x4 dqt[4];
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) dqt[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-          for (int ks = 0; ks < nks; ++ks) {
-            const bf16x8 fa = frag_tr(dSs, PS, ks * 32, 16 * w, lane);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-              dqt[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, frag_tr(Ks, QS, ks * 32, nt * 16, lane), dqt[nt], 0, 0,
-                                                                0);
-          }
-#pragma unroll
-          for (int j = 0; j < NQB; ++j)
-            if (j == qb) {  // wave-uniform select keeps dq[][] in registers (no runtime-indexed vector array)
-#pragma unroll
-              for (int nt = 0; nt < 4; ++nt) dq[j][nt] += dqt[nt];
-            }
-        }
-        __syncthreads();  // Qs / dOs / dSs are re-filled by the next pair
-      }
-    }
-    // ---- dK, dV of this key block: dkT[dt][r] = dK[key = keyw + i16][d = dt*16 + 4g + r]
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      u32x2 pk, pv;
-      pk[0] = pack2(dkT[dt][0], dkT[dt][1]);
-      pk[1] = pack2(dkT[dt][2], dkT[dt][3]);
-      pv[0] = pack2(dvT[dt][0], dvT[dt][1]);
-      pv[1] = pack2(dvT[dt][2], dvT[dt][3]);
-      *reinterpret_cast<u32x2*>(mine + i16 * PS + (dt * 16 + g * 4) * 2) = pk;
-      *reinterpret_cast<u32x2*>(mine + i16 * PS + 128 + (dt * 16 + g * 4) * 2) = pv;
-    }
-    if (has_keys) {
-      const int nv = min(16, S - keyw);
-      store_rows16(mine, PS, dbase_g + H, ld, keyw, nv, lane);
-      store_rows16(mine + 128, PS, dbase_g + 2 * H, ld, keyw, nv, lane);
-    }
-  }
-
-  // ---- dQ of every query block: dq[qb][nt][r] = dQ[q = qb*128 + 16w + 4g + r][d = nt*16 + i16]
-#pragma unroll
-  for (int qb = 0; qb < NQB; ++qb) {
-    const int qw = qb * TB + 16 * w;
-    if (qw < S) {  // wave-uniform
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          *reinterpret_cast<bf16_t*>(mine + (g * 4 + r) * PS + (nt * 16 + i16) * 2) = f2bf(dq[qb][nt][r]);
-      store_rows16(mine, PS, dbase_g, ld, qw, min(16, S - qw), lane);
-    }
   }
 }
 
-// ------------------------------------------------------------------------------------ backward, split by role
-// No sequence-length ceiling in the structure: the one-pass kernel above holds the dQ accumulators of EVERY query block
-// (NQB <= 4), these two roles hold one block's each.
-//   dK/dV role: one workgroup per (head, sequence, 128-key block).  K and V are staged once, the query blocks are swept
-//               (from kb on when causal) with phase A only; dK^t / dV^t accumulate in MFMA accumulators in ascending
-//               query-block order.  No dS image, no dQ.
-//   dQ role:    one workgroup per (head, sequence, 128-query block).  dO, lse and delta are staged once, the key blocks are
-//               swept (up to qb when causal); S, dP and dS are recomputed, dS crosses LDS as above and phase B adds a
-//               fresh dqt per key block in ascending key-block order.
-// Nothing is summed across workgroups (no atomics, no workspace) and every element sees the one-pass kernel's products
-// in the one-pass kernel's order.  7 matmuls per (key, query) pair instead of 5, for nkb + nqb workgroups per
-// (head, sequence) instead of one.  Both roles use the ALIAS layout (K | V | Q | dO, dS^t over V and Q, 75 KiB) and stay
-// within 128 registers: two workgroups per CU, and one grid can carry both roles.  lse / delta live in LDS for ONE
-// 128-query block at a time, so LDS use does not grow with S.
+// A workgroup's memory latency is hidden by at most one other workgroup on its CU (none when S > 128): everything the
+// first (key block, query block) pair needs - the K, V, Q, dO tiles and the row constants' inputs (O rows for delta, NROWS
+// of lse from q0 on) - is REQUESTED together into registers and stored to LDS afterwards: one HBM round trip in front of
+// the first MFMA instead of three.  With packed sequences (mean length 72 of 128) most workgroups have exactly one pair.
+template <int NROWS>
+struct PairRegs {
+  StageRegs k, v, q, dO, o;
+  float lse[(NROWS + TNT - 1) / TNT];
+};
+template <int NROWS>
+__device__ __forceinline__ void load_q_block(const BwdBlock& c, int q0, int t, PairRegs<NROWS>& r) {
+  stage_load(r.q, c.base, c.ld, q0, c.S, t);
+  stage_load(r.dO, c.dobase, c.H, q0, c.S, t);
+  stage_load(r.o, c.obase, c.H, q0, c.S, t);
+#pragma unroll
+  for (int j = 0; j * TNT < NROWS; ++j) {
+    const int i = t + TNT * j;
+    r.lse[j] = (i < NROWS && q0 + i < c.S) ? c.lse_row[q0 + i] : 0.f;
+  }
+}
+template <int NROWS>
+__device__ __forceinline__ void load_first_pair(const BwdBlock& c, int k0, int q0, PairRegs<NROWS>& r) {
+  stage_load(r.k, c.base + c.H, c.ld, k0, c.S, c.t);
+  stage_load(r.v, c.base + 2 * c.H, c.ld, k0, c.S, c.t);
+  load_q_block(c, q0, c.t, r);
+}
+// the row constants of the requested query rows: delta of the first 128, lse of all NROWS
+template <int NROWS>
+__device__ __forceinline__ void store_row_consts(const BwdBlock& c, int t, const PairRegs<NROWS>& r) {
+  delta_rows(r.o, r.dO, c.dels, t);
+#pragma unroll
+  for (int j = 0; j * TNT < NROWS; ++j)
+    if (t + TNT * j < NROWS) c.lses[t + TNT * j] = r.lse[j];
+}
+template <int NROWS>
+__device__ __forceinline__ void store_first_pair(const BwdBlock& c, const PairRegs<NROWS>& r) {
+  stage_store(r.k, c.Ks, c.t);
+  stage_store(r.v, c.Vs, c.t);
+  stage_store(r.q, c.Qs, c.t);
+  stage_store(r.dO, c.dOs, c.t);
+  store_row_consts(c, c.t, r);
+}
 
-// rows of one 128-query block: delta[row] = sum_d dO[row, d] O[row, d] from the requested registers (8 lanes per row; the
-// (row, chunk) map is stage_load's), summed in the one-pass kernel's order
-__device__ __forceinline__ void split_delta(const StageRegs& po, const StageRegs& pdo, float* dels, int t) {
+// validity of the 128 keys from k0 (folds key < S)
+__device__ __forceinline__ void fill_kms(const AttnBwd& a, const BwdBlock& c, int k0) {
+  if (c.t < TB) c.kms[c.t] = (k0 + c.t < c.S && (!a.kmask || a.kmask[c.b * a.Sp + k0 + c.t] != 0)) ? 1 : 0;
+}
+
+// this wave's 16 keys of the staged K and V as B operands (n = key)
+__device__ __forceinline__ void key_frags(const BwdBlock& c, int lane, bf16x8 (&fk)[2], bf16x8 (&fv)[2]) {
 #pragma unroll
-  for (int i = 0; i < 1024 / TNT; ++i) {
-    const int idx = t + TNT * i;
-    const int row = idx >> 3, c = idx & 7;
-    const bf16x8 a = __builtin_bit_cast(bf16x8, po.v[i]);
-    const bf16x8 gg = __builtin_bit_cast(bf16x8, pdo.v[i]);
-    float d = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) d += (float)a[e] * (float)gg[e];
-    d += __shfl_xor(d, 1);
-    d += __shfl_xor(d, 2);
-    d += __shfl_xor(d, 4);
-    if (c == 0) dels[row] = d;
+  for (int kk = 0; kk < 2; ++kk) {
+    fk[kk] = frag_rows64(c.Ks, 16 * c.w, kk, lane);
+    fv[kk] = frag_rows64(c.Vs, 16 * c.w, kk, lane);
   }
 }
 
 // One 32-query step of phase A for this wave's 16 keys: S and dP with the key on the lane -> the dropped probabilities
-// and dS of two stacked 16x16 tiles.  lses / dels hold the rows of the CURRENT query block (q0 ..).
-__device__ __forceinline__ void split_pair_step(const unsigned char* Qs, const unsigned char* dOs, const float* lses,
-                                                const float* dels, const bf16x8 (&fk)[2], const bf16x8 (&fv)[2], int s,
-                                                int q0, int S, int Sp, int key, bool kvalid, int causal, unsigned bh,
-                                                const Drop& drop, int lane, float (&pd)[2][4], float (&ds)[2][4]) {
+// and dS of two stacked 16x16 tiles.  lses / dels point at the rows of the CURRENT query block (q0 ..).
+__device__ __forceinline__ void pair_step(const AttnBwd& a, const BwdBlock& c, const float* lses, const float* dels,
+                                          const bf16x8 (&fk)[2], const bf16x8 (&fv)[2], int s, int q0, int key,
+                                          bool kvalid, int lane, float (&pd)[2][4], float (&ds)[2][4]) {
   const float scale = 0.125f;
   const int g = lane >> 4;
   f32x4 sa[2], da[2];
@@ -706,10 +524,10 @@ __device__ __forceinline__ void split_pair_step(const unsigned char* Qs, const u
     sa[tt] = da[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      sa[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(Qs, (2 * s + tt) * 16, kk, lane), fk[kk], sa[tt], 0, 0,
-                                                       0);
-      da[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(dOs, (2 * s + tt) * 16, kk, lane), fv[kk], da[tt], 0, 0,
-                                                       0);
+      sa[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(c.Qs, (2 * s + tt) * 16, kk, lane), fk[kk], sa[tt], 0,
+                                                       0, 0);
+      da[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(c.dOs, (2 * s + tt) * 16, kk, lane), fv[kk], da[tt], 0,
+                                                       0, 0);
     }
   }
 #pragma unroll
@@ -720,66 +538,236 @@ __device__ __forceinline__ void split_pair_step(const unsigned char* Qs, const u
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int q = q0 + ql + r;
-      const bool ok = kvalid && q < S && (!causal || key <= q);
+      const bool ok = kvalid && q < c.S && (!a.causal || key <= q);
       const float pu = ok ? __expf(sa[tt][r] * scale - l4[r]) : 0.f;  // undropped probability
-      const float m = drop.on() ? drop.mul((bh * Sp + q) * Sp + key) : 1.f;
+      // (the key runs along the lanes here, so each element has its own pair hash)
+      const float m = a.drop.on() ? a.drop.mul((c.bh * a.Sp + q) * a.Sp + key) : 1.f;
       ds[tt][r] = pu * (da[tt][r] * m - d4[r]) * scale;               // dP = dP_dropped * m
       pd[tt][r] = pu * m;                                              // dV uses the dropped probabilities
     }
   }
 }
 
-__device__ __forceinline__ void split_dkv_role(unsigned char* smem, const bf16_t* __restrict__ qkv,
-                                               const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO,
-                                               const float* __restrict__ lse_i, const int* __restrict__ kmask, int S,
-                                               int heads, int causal, bf16_t* __restrict__ dqkv, const Drop& drop,
-                                               const int* __restrict__ cu, int Sp, int kb) {
-  unsigned char* Ks = smem;
-  unsigned char* Vs = smem + TILE_QKV;
-  unsigned char* Qs = smem + 2 * TILE_QKV;
-  unsigned char* dOs = smem + 3 * TILE_QKV;
-  float* lses = reinterpret_cast<float*>(smem + 4 * TILE_QKV);  // [128]: the current query block's
-  float* dels = lses + TB;                                      // [128]
-  unsigned char* kms = reinterpret_cast<unsigned char*>(dels + TB);  // [128]
+// the step's P and dS accumulators are the B operands of dV^t += dO^t P and dK^t += Q^t dS
+__device__ __forceinline__ void dkv_step(const BwdBlock& c, int s, const float (&pd)[2][4], const float (&ds)[2][4],
+                                         f32x4 (&dvT)[4], f32x4 (&dkT)[4]) {
+  const bf16x8 fp = pack_acc(pd[0], pd[1]);
+  const bf16x8 fds = pack_acc(ds[0], ds[1]);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    dvT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(c.dOs, QS, s * 32, dt * 16, c.lane), fp, dvT[dt], 0, 0, 0);
+    dkT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(c.Qs, QS, s * 32, dt * 16, c.lane), fds, dkT[dt], 0, 0, 0);
+  }
+}
 
-  const int h = blockIdx.x, b = blockIdx.y;
-  const int row0 = cu ? cu[b] : b * Sp;  // packed rows: see the forward
-  if (cu) S = min(S, cu[b + 1] - row0);
+__device__ __forceinline__ u32x2 pack_ds(const float (&ds)[4]) {
+  u32x2 pk;
+  pk[0] = pack2(ds[0], ds[1]);
+  pk[1] = pack2(ds[2], ds[3]);
+  return pk;
+}
+// a wave with no real key in its rows: the dQ product must read zeros there
+__device__ __forceinline__ void zero_dsp(u32x2 (&dsp)[8]) {
+#pragma unroll
+  for (int mi = 0; mi < 8; ++mi) dsp[mi] = (u32x2){0u, 0u};
+}
+// the held dS of this wave's 16 keys -> its rows of the dS^t image
+__device__ __forceinline__ void write_ds_image(unsigned char* mine, const u32x2 (&dsp)[8], int i16, int g) {
+#pragma unroll
+  for (int mi = 0; mi < 8; ++mi) *reinterpret_cast<u32x2*>(mine + i16 * PS + (mi * 16 + g * 4) * 2) = dsp[mi];
+}
+
+// phase B of one (key block, query block) pair: dqt[q][d] = dS[q][key] K[key][d] for this wave's 16 queries of the block,
+// a fresh partial per key block
+__device__ __forceinline__ void phase_b(const BwdBlock& c, int k0, bool diagonal, f32x4 (&dqt)[4]) {
+  int nks = (min(TB, c.S - k0) + 31) >> 5;
+  if (diagonal) nks = min(nks, (c.w >> 1) + 1);
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) dqt[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int ks = 0; ks < nks; ++ks) {
+    const bf16x8 fa = frag_tr(c.dSs, PS, ks * 32, 16 * c.w, c.lane);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+      dqt[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, frag_tr(c.Ks, QS, ks * 32, nt * 16, c.lane), dqt[nt], 0, 0, 0);
+  }
+}
+
+// dK, dV of a key block: dkT[dt][r] = dK[key = keyw + i16][d = dt*16 + 4g + r], through the wave's own rows
+__device__ __forceinline__ void store_dkv(const BwdBlock& c, const f32x4 (&dkT)[4], const f32x4 (&dvT)[4], int keyw) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    u32x2 pk, pv;
+    pk[0] = pack2(dkT[dt][0], dkT[dt][1]);
+    pk[1] = pack2(dkT[dt][2], dkT[dt][3]);
+    pv[0] = pack2(dvT[dt][0], dvT[dt][1]);
+    pv[1] = pack2(dvT[dt][2], dvT[dt][3]);
+    *reinterpret_cast<u32x2*>(c.mine + c.i16 * PS + (dt * 16 + c.g * 4) * 2) = pk;
+    *reinterpret_cast<u32x2*>(c.mine + c.i16 * PS + 128 + (dt * 16 + c.g * 4) * 2) = pv;
+  }
+  if (keyw < c.S) {  // wave-uniform
+    const int nv = min(16, c.S - keyw);
+    store_rows16(c.mine, PS, c.dbase_g + c.H, c.ld, keyw, nv, c.lane);
+    store_rows16(c.mine + 128, PS, c.dbase_g + 2 * c.H, c.ld, keyw, nv, c.lane);
+  }
+}
+
+// dQ of a query block: dq[nt][r] = dQ[q = qw + 4g + r][d = nt*16 + i16]
+__device__ __forceinline__ void store_dq(const BwdBlock& c, const f32x4 (&dq)[4], int qw) {
+  if (qw < c.S) {  // wave-uniform
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        *reinterpret_cast<bf16_t*>(c.mine + (c.g * 4 + r) * PS + (nt * 16 + c.i16) * 2) = f2bf(dq[nt][r]);
+    store_rows16(c.mine, PS, c.dbase_g, c.ld, qw, min(16, c.S - qw), c.lane);
+  }
+}
+
+// ------------------------------------------------------------------------------------ backward, one pass (S <= 512)
+template <int NQB, bool ALIAS>
+__global__ __launch_bounds__(TNT, ALIAS ? 4 : 2) void attn_bwd_tiled_kernel(const AttnBwd a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const BwdBlock c = bwd_block<NQB, ALIAS>(smem, a);
+  const int S = c.S, t = c.t, w = c.w;
+  if (S <= 0) return;
+
+  // row constants of every query: lse and delta.  Rows of the first query block come with the first pair (0 in both
+  // mask modes), later blocks' delta from memory.
+  PairRegs<NQB * TB> first;
+  load_first_pair(c, 0, 0, first);
+  store_row_consts(c, t, first);
+  for (int idx = t + 1024; idx < NQB * TB * 8; idx += TNT) {
+    const int row = idx >> 3, ch = idx & 7;
+    float d = 0.f;
+    if (row < S) {
+      const bf16x8 o8 = *reinterpret_cast<const bf16x8*>(c.obase + (size_t)row * c.H + ch * 8);
+      const bf16x8 gg = *reinterpret_cast<const bf16x8*>(c.dobase + (size_t)row * c.H + ch * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) d += (float)o8[e] * (float)gg[e];
+    }
+    d += __shfl_xor(d, 1);
+    d += __shfl_xor(d, 2);
+    d += __shfl_xor(d, 4);
+    if (ch == 0) c.dels[row] = d;
+  }
+
+  f32x4 dq[NQB][4];
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) dq[qb][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const int nblk = NQB == 1 ? 1 : (S + TB - 1) / TB;  // key blocks == query blocks (<= NQB; S > 0 here)
+
+  for (int kb = 0; kb < nblk; ++kb) {
+    const int k0 = kb * TB;
+    // (the barrier that closes the previous pair protects Ks / Vs / kms)
+    if (kb == 0) {   // requested at the top.  (The tile stores stay in here: in straight line behind the requests the
+                     // compiler waits three times among the ten loads instead of once after them.)
+      stage_store(first.k, c.Ks, t);
+      stage_store(first.v, c.Vs, t);
+      stage_store(first.q, c.Qs, t);
+      stage_store(first.dO, c.dOs, t);
+    } else {
+      stage_rows(c.Ks, c.base + c.H, c.ld, k0, S, t);
+      stage_rows(c.Vs, c.base + 2 * c.H, c.ld, k0, S, t);
+    }
+    fill_kms(a, c, k0);
+    __syncthreads();
+    const int keyw = k0 + 16 * w;            // this wave's first key
+    const bool has_keys = keyw < S;          // wave-uniform
+    const int key = keyw + c.i16;
+    bf16x8 fk[2], fv[2];                     // loop-invariant over the query blocks
+    key_frags(c, c.lane, fk, fv);
+    const bool kvalid = key < S && c.kms[16 * w + c.i16];
+    f32x4 dvT[4], dkT[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) dvT[dt] = dkT[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    // runtime loop (one copy of the body); only the dQ accumulators are indexed statically, at the end of the pair
+#pragma unroll 1
+    for (int qb = a.causal ? kb : 0; qb < nblk; ++qb) {
+      const int q0 = qb * TB;
+      if (kb != 0 || qb != 0) {   // (pair (0, 0) was staged with the key block)
+        stage_rows(c.Qs, c.base, c.ld, q0, S, t);
+        stage_rows(c.dOs, c.dobase, c.H, q0, S, t);
+        __syncthreads();
+      }
+      // ---- phase A: S, dP (key on the lane) -> P, dS -> dV^t, dK^t; dS^t to LDS
+      const int nqt = min(8, (S - q0 + 15) >> 4);          // 16-query tiles with a real row
+      // on the diagonal block queries below this wave's first key see none of its keys
+      const int mi_lo = (a.causal && qb == kb) ? w : 0;
+      u32x2 dsp[ALIAS ? 8 : 1];
+      auto phase_a = [&](const int s) {
+        float pd[2][4], ds[2][4] = {};
+        if (2 * s < nqt && 2 * s + 1 >= mi_lo) {
+          pair_step(a, c, c.lses + q0, c.dels + q0, fk, fv, s, q0, key, kvalid, c.lane, pd, ds);
+          dkv_step(c, s, pd, ds, dvT, dkT);
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          if constexpr (ALIAS) dsp[2 * s + tt] = pack_ds(ds[tt]);   // V / Q are still being read: held until the barrier
+          else *reinterpret_cast<u32x2*>(c.mine + c.i16 * PS + ((2 * s + tt) * 16 + c.g * 4) * 2) = pack_ds(ds[tt]);
+        }
+      };
+      if constexpr (ALIAS) {
+        if (has_keys) {
+#pragma unroll
+          for (int s = 0; s < 4; ++s) phase_a(s);
+        } else {
+          zero_dsp(dsp);
+        }
+        __syncthreads();  // every wave is done with V and Q: their space takes the dS^t image
+        write_ds_image(c.mine, dsp, c.i16, c.g);
+      } else if (has_keys) {
+#pragma unroll 1
+        for (int s = 0; s < 4; ++s) phase_a(s);
+      } else {  // no real key in this wave's rows: the dQ product must read zeros there
+#pragma unroll
+        for (int mi = 0; mi < 8; ++mi)
+          *reinterpret_cast<u32x2*>(c.mine + c.i16 * PS + (mi * 16 + c.g * 4) * 2) = (u32x2){0u, 0u};
+      }
+      __syncthreads();
+      if (q0 + 16 * w < S) {
+        f32x4 dqt[4];
+        phase_b(c, k0, a.causal && qb == kb, dqt);
+#pragma unroll
+        for (int j = 0; j < NQB; ++j)
+          if (j == qb) {  // wave-uniform select keeps dq[][] in registers (no runtime-indexed vector array)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) dq[j][nt] += dqt[nt];
+          }
+      }
+      __syncthreads();  // Qs / dOs / dSs are re-filled by the next pair
+    }
+    store_dkv(c, dkT, dvT, keyw);
+  }
+
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb) store_dq(c, dq[qb], qb * TB + 16 * w);
+}
+
+// ------------------------------------------------------------------------------------ backward, split by role (S <= 1024)
+// 7 matmuls per (key, query) pair instead of 5, for nkb + nqb workgroups per (head, sequence) instead of one.  Both roles
+// use the ALIAS layout and stay within 128 registers: two workgroups per CU, and one grid can carry both roles.  lse /
+// delta live in LDS for ONE 128-query block at a time, so LDS use does not grow with S.
+
+// dK/dV role: phase A only; dK^t / dV^t accumulate in ascending query-block order.  No dS image, no dQ.
+__device__ __forceinline__ void dkv_role(unsigned char* smem, const AttnBwd& a, int kb) {
+  const BwdBlock c = bwd_block<1, true>(smem, a);
+  const int S = c.S, t = c.t, w = c.w;
   const int k0 = kb * TB;
   if (k0 >= S) return;  // block-uniform: a short (or empty) sequence has no such key block
-  const int H = heads * DH, ld = 3 * H;
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int g = lane >> 4, i16 = lane & 15;
-  const bf16_t* base = qkv + (size_t)row0 * ld + h * DH;
-  const bf16_t* obase = O + (size_t)row0 * H + h * DH;
-  const bf16_t* dobase = dO + (size_t)row0 * H + h * DH;
-  bf16_t* dbase_g = dqkv + (size_t)row0 * ld + h * DH;
-  const float* lse_row = lse_i + ((size_t)b * heads + h) * Sp;
-  const unsigned bh = (unsigned)b * heads + h;
-
   const int nblk = (S + TB - 1) / TB;
-  const int qb0 = causal ? kb : 0;
-  // everything the first pair needs is requested before anything waits (one HBM round trip in front of the first MFMA)
-  {
-    StageRegs pk, pv, pq, pdo, po;
-    stage_load(pk, base + H, ld, k0, S, t);
-    stage_load(pv, base + 2 * H, ld, k0, S, t);
-    stage_load(pq, base, ld, qb0 * TB, S, t);
-    stage_load(pdo, dobase, H, qb0 * TB, S, t);
-    stage_load(po, obase, H, qb0 * TB, S, t);
-    const float plse = (t < TB && qb0 * TB + t < S) ? lse_row[qb0 * TB + t] : 0.f;
-    stage_store(pk, Ks, t);
-    stage_store(pv, Vs, t);
-    stage_store(pq, Qs, t);
-    stage_store(pdo, dOs, t);
-    split_delta(po, pdo, dels, t);
-    if (t < TB) lses[t] = plse;
-  }
-  if (t < TB) kms[t] = (k0 + t < S && (!kmask || kmask[b * Sp + k0 + t] != 0)) ? 1 : 0;
+  const int qb0 = a.causal ? kb : 0;
+  PairRegs<TB> r;
+  load_first_pair(c, k0, qb0 * TB, r);
+  store_first_pair(c, r);
+  fill_kms(a, c, k0);
   const int keyw = k0 + 16 * w;            // this wave's first key
   const bool has_keys = keyw < S;          // wave-uniform
-  const int key = keyw + i16;
+  const int key = keyw + c.i16;
   f32x4 dvT[4], dkT[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) dvT[dt] = dkT[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -794,119 +782,49 @@ __device__ __forceinline__ void split_dkv_role(unsigned char* smem, const bf16_t
     if (qb != qb0) {  // (the first block came with K and V)
       int tl = t;
       asm volatile("" : "+v"(tl));
-      StageRegs pq, pdo, po;
-      stage_load(pq, base, ld, q0, S, tl);
-      stage_load(pdo, dobase, H, q0, S, tl);
-      stage_load(po, obase, H, q0, S, tl);
-      const float plse = (tl < TB && q0 + tl < S) ? lse_row[q0 + tl] : 0.f;
-      stage_store(pq, Qs, tl);
-      stage_store(pdo, dOs, tl);
-      split_delta(po, pdo, dels, tl);
-      if (tl < TB) lses[tl] = plse;
+      load_q_block(c, q0, tl, r);
+      stage_store(r.q, c.Qs, tl);
+      stage_store(r.dO, c.dOs, tl);
+      store_row_consts(c, tl, r);
     }
     __syncthreads();
-    const bool kvalid = key < S && kms[16 * w + i16];
+    const bool kvalid = key < S && c.kms[16 * w + c.i16];
     if (has_keys) {
-      bf16x8 fk[2], fv[2];                   // B operands (n = key)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        fk[kk] = frag_rows64(Ks, 16 * w, kk, lane);
-        fv[kk] = frag_rows64(Vs, 16 * w, kk, lane);
-      }
+      bf16x8 fk[2], fv[2];
+      key_frags(c, c.lane, fk, fv);
       const int nqt = min(8, (S - q0 + 15) >> 4);          // 16-query tiles with a real row
       // on the diagonal block queries below this wave's first key see none of its keys
-      const int mi_lo = (causal && qb == kb) ? w : 0;
+      const int mi_lo = (a.causal && qb == kb) ? w : 0;
 #pragma unroll 1
       for (int s = 0; s < 4; ++s) {
         if (2 * s < nqt && 2 * s + 1 >= mi_lo) {
           float pd[2][4], ds[2][4];
-          split_pair_step(Qs, dOs, lses, dels, fk, fv, s, q0, S, Sp, key, kvalid, causal, bh, drop, lane, pd, ds);
-          const bf16x8 fp = pack_acc(pd[0], pd[1]);
-          const bf16x8 fds = pack_acc(ds[0], ds[1]);
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) {
-            dvT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(dOs, QS, s * 32, dt * 16, lane), fp, dvT[dt], 0,
-                                                              0, 0);
-            dkT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(Qs, QS, s * 32, dt * 16, lane), fds, dkT[dt], 0,
-                                                              0, 0);
-          }
+          pair_step(a, c, c.lses, c.dels, fk, fv, s, q0, key, kvalid, c.lane, pd, ds);
+          dkv_step(c, s, pd, ds, dvT, dkT);
         }
       }
     }
     __syncthreads();  // Qs / dOs / lses / dels are re-filled by the next block
   }
-  // ---- dK, dV of this key block: dkT[dt][r] = dK[key = keyw + i16][d = dt*16 + 4g + r]; staged in the wave's own 16
-  // rows of the (now free) Q / dO space
-  unsigned char* mine = Qs + (16 * w) * PS;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    u32x2 pk, pv;
-    pk[0] = pack2(dkT[dt][0], dkT[dt][1]);
-    pk[1] = pack2(dkT[dt][2], dkT[dt][3]);
-    pv[0] = pack2(dvT[dt][0], dvT[dt][1]);
-    pv[1] = pack2(dvT[dt][2], dvT[dt][3]);
-    *reinterpret_cast<u32x2*>(mine + i16 * PS + (dt * 16 + g * 4) * 2) = pk;
-    *reinterpret_cast<u32x2*>(mine + i16 * PS + 128 + (dt * 16 + g * 4) * 2) = pv;
-  }
-  if (has_keys) {
-    const int nv = min(16, S - keyw);
-    store_rows16(mine, PS, dbase_g + H, ld, keyw, nv, lane);
-    store_rows16(mine + 128, PS, dbase_g + 2 * H, ld, keyw, nv, lane);
-  }
+  store_dkv(c, dkT, dvT, keyw);  // (every image is free by now)
 }
 
-__device__ __forceinline__ void split_dq_role(unsigned char* smem, const bf16_t* __restrict__ qkv,
-                                              const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO,
-                                              const float* __restrict__ lse_i, const int* __restrict__ kmask, int S,
-                                              int heads, int causal, bf16_t* __restrict__ dqkv, const Drop& drop,
-                                              const int* __restrict__ cu, int Sp, int qb) {
-  unsigned char* Ks = smem;
-  unsigned char* Vs = smem + TILE_QKV;
-  unsigned char* Qs = smem + 2 * TILE_QKV;
-  unsigned char* dOs = smem + 3 * TILE_QKV;
-  static_assert(TILE_P <= 2 * TILE_QKV, "the dS^t image must fit where V and Q were");
-  unsigned char* dSs = Vs;                                      // dS^t image [128 keys][128 queries] over V and Q
-  float* lses = reinterpret_cast<float*>(smem + 4 * TILE_QKV);  // [128]: this query block's
-  float* dels = lses + TB;                                      // [128]
-  unsigned char* kms = reinterpret_cast<unsigned char*>(dels + TB);  // [128]
-
-  const int h = blockIdx.x, b = blockIdx.y;
-  const int row0 = cu ? cu[b] : b * Sp;  // packed rows: see the forward
-  if (cu) S = min(S, cu[b + 1] - row0);
+// dQ role: dO, lse and delta are staged once; S, dP and dS are recomputed per key block, dS crosses LDS and phase B adds a
+// fresh dqt per key block in ascending key-block order.
+__device__ __forceinline__ void dq_role(unsigned char* smem, const AttnBwd& a, int qb) {
+  const BwdBlock c = bwd_block<1, true>(smem, a);
+  const int S = c.S, t = c.t, w = c.w;
   const int q0_ = qb * TB;
   if (q0_ >= S) return;  // block-uniform: a short (or empty) sequence has no such query block
-  const int H = heads * DH, ld = 3 * H;
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int g = lane >> 4, i16 = lane & 15;
-  const bf16_t* base = qkv + (size_t)row0 * ld + h * DH;
-  const bf16_t* obase = O + (size_t)row0 * H + h * DH;
-  const bf16_t* dobase = dO + (size_t)row0 * H + h * DH;
-  bf16_t* dbase_g = dqkv + (size_t)row0 * ld + h * DH;
-  const unsigned bh = (unsigned)b * heads + h;
-
-  {  // the first pair and the block's row constants, requested together
-    StageRegs pk, pv, pq, pdo, po;
-    stage_load(pk, base + H, ld, 0, S, t);
-    stage_load(pv, base + 2 * H, ld, 0, S, t);
-    stage_load(pq, base, ld, q0_, S, t);
-    stage_load(pdo, dobase, H, q0_, S, t);
-    stage_load(po, obase, H, q0_, S, t);
-    const float plse = (t < TB && q0_ + t < S) ? lse_i[((size_t)b * heads + h) * Sp + q0_ + t] : 0.f;
-    split_delta(po, pdo, dels, t);
-    if (t < TB) lses[t] = plse;
-    stage_store(pk, Ks, t);
-    stage_store(pv, Vs, t);
-    stage_store(pq, Qs, t);
-    stage_store(pdo, dOs, t);  // stays for every key block
-  }
+  PairRegs<TB> r;
+  load_first_pair(c, 0, q0_, r);
+  store_first_pair(c, r);  // (dO, lse and delta stay for every key block)
 
   f32x4 dq[4];
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) dq[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int nkb = causal ? qb + 1 : (S + TB - 1) / TB;
+  const int nkb = a.causal ? qb + 1 : (S + TB - 1) / TB;
   const int nqt = min(8, (S - q0_ + 15) >> 4);  // 16-query tiles with a real row
-  unsigned char* mine = dSs + (16 * w) * PS;   // this wave's own 16 rows of the dS^t image (also its store staging)
 
 #pragma unroll 1
   for (int kb = 0; kb < nkb; ++kb) {
@@ -919,119 +837,73 @@ __device__ __forceinline__ void split_dq_role(unsigned char* smem, const bf16_t*
     if (kb != 0) {  // V and Q were overwritten by the dS^t image
       int tl = t;   // (the per-thread row addresses are rebuilt here too)
       asm volatile("" : "+v"(tl));
-      stage_rows(Ks, base + H, ld, k0, S, tl);
-      stage_rows(Vs, base + 2 * H, ld, k0, S, tl);
-      stage_rows(Qs, base, ld, q0, S, tl);
+      stage_rows(c.Ks, c.base + c.H, c.ld, k0, S, tl);
+      stage_rows(c.Vs, c.base + 2 * c.H, c.ld, k0, S, tl);
+      stage_rows(c.Qs, c.base, c.ld, q0, S, tl);
     }
-    if (t < TB) kms[t] = (k0 + t < S && (!kmask || kmask[b * Sp + k0 + t] != 0)) ? 1 : 0;
+    fill_kms(a, c, k0);
     __syncthreads();
     const int keyw = k0 + 16 * w;            // this wave's first key
-    const bool has_keys = keyw < S;          // wave-uniform
-    int ll = lane;   // (so are the per-lane tile offsets)
+    int ll = c.lane;   // (so are the per-lane tile offsets)
     asm volatile("" : "+v"(ll));
     const int gl = ll >> 4, il = ll & 15;
     const int key = keyw + il;
-    const bool kvalid = key < S && kms[16 * w + il];
-    const int mi_lo = (causal && qb == kb) ? w : 0;
+    const bool kvalid = key < S && c.kms[16 * w + il];
+    const int mi_lo = (a.causal && qb == kb) ? w : 0;
     u32x2 dsp[8];  // V / Q are still being read by other waves: held until the barrier
-    if (has_keys) {
+    if (keyw < S) {  // wave-uniform
       bf16x8 fk[2], fv[2];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        fk[kk] = frag_rows64(Ks, 16 * w, kk, ll);
-        fv[kk] = frag_rows64(Vs, 16 * w, kk, ll);
-      }
+      key_frags(c, ll, fk, fv);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        float pd[2][4], ds[2][4];
-        if (2 * s < nqt && 2 * s + 1 >= mi_lo) {
-          split_pair_step(Qs, dOs, lses, dels, fk, fv, s, q0, S, Sp, key, kvalid, causal, bh, drop, ll, pd, ds);
-        } else {
+        float pd[2][4], ds[2][4] = {};
+        if (2 * s < nqt && 2 * s + 1 >= mi_lo) pair_step(a, c, c.lses, c.dels, fk, fv, s, q0, key, kvalid, ll, pd, ds);
 #pragma unroll
-          for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ds[tt][r] = 0.f;
-        }
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-          dsp[2 * s + tt][0] = pack2(ds[tt][0], ds[tt][1]);
-          dsp[2 * s + tt][1] = pack2(ds[tt][2], ds[tt][3]);
-        }
+        for (int tt = 0; tt < 2; ++tt) dsp[2 * s + tt] = pack_ds(ds[tt]);
       }
-    } else {  // no real key in this wave's rows: the dQ product must read zeros there
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi) dsp[mi] = (u32x2){0u, 0u};
+    } else {
+      zero_dsp(dsp);
     }
     __syncthreads();  // every wave is done with V and Q: their space takes the dS^t image
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) *reinterpret_cast<u32x2*>(mine + il * PS + (mi * 16 + gl * 4) * 2) = dsp[mi];
+    write_ds_image(c.mine, dsp, il, gl);
     __syncthreads();
-    // ---- phase B: dQ[q][d] += dS[q][key] K[key][d] for this wave's 16 queries of the block
     if (q0 + 16 * w < S) {
-      int nks = (min(TB, S - k0) + 31) >> 5;
-      if (causal && qb == kb) nks = min(nks, (w >> 1) + 1);
       f32x4 dqt[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) dqt[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-      for (int ks = 0; ks < nks; ++ks) {
-        const bf16x8 fa = frag_tr(dSs, PS, ks * 32, 16 * w, lane);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-          dqt[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, frag_tr(Ks, QS, ks * 32, nt * 16, lane), dqt[nt], 0, 0, 0);
-      }
+      phase_b(c, k0, a.causal && qb == kb, dqt);
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) dq[nt] += dqt[nt];
     }
     __syncthreads();  // Ks / Vs / Qs are re-filled by the next key block
   }
-
-  // ---- dQ of this query block: dq[nt][r] = dQ[q = q0 + 16w + 4g + r][d = nt*16 + i16]
-  const int qw = q0_ + 16 * w;
-  if (qw < S) {  // wave-uniform
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        *reinterpret_cast<bf16_t*>(mine + (g * 4 + r) * PS + (nt * 16 + i16) * 2) = f2bf(dq[nt][r]);
-    store_rows16(mine, PS, dbase_g, ld, qw, min(16, S - qw), lane);
-  }
+  store_dq(c, dq, q0_ + 16 * w);
 }
-
-#define PGCA_SPLIT_PARAMS                                                                                              \
-  const bf16_t *__restrict__ qkv, const bf16_t *__restrict__ O, const bf16_t *__restrict__ dO,                        \
-      const float *__restrict__ lse_i, const int *__restrict__ kmask, int S, int heads, int causal,                    \
-      bf16_t *__restrict__ dqkv, Drop drop, const int *__restrict__ cu, int Sp
-#define PGCA_SPLIT_ARGS qkv, O, dO, lse_i, kmask, S, heads, causal, dqkv, drop, cu, Sp
 
 // Both roles in one grid of 2 * nblk workgroups per (head, sequence); the heaviest first when causal: key block 0 sweeps
 // every query block, the last query block every key block.  (A launch per role was measured and lost at every shape.)
-__global__ __launch_bounds__(TNT, 4) void attn_bwd_split_kernel(PGCA_SPLIT_PARAMS) {
+__global__ __launch_bounds__(TNT, 4) void attn_bwd_split_kernel(const AttnBwd a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int nblk = gridDim.z >> 1;
-  if ((int)blockIdx.z < nblk) split_dkv_role(smem, PGCA_SPLIT_ARGS, blockIdx.z);
-  else split_dq_role(smem, PGCA_SPLIT_ARGS, gridDim.z - 1 - blockIdx.z);
+  if ((int)blockIdx.z < nblk) dkv_role(smem, a, blockIdx.z);
+  else dq_role(smem, a, gridDim.z - 1 - blockIdx.z);
 }
 
 constexpr size_t TFWD_LDS = 2 * TILE_QKV + TB;
-constexpr size_t tbwd_lds(int nqb) { return 4 * TILE_QKV + TILE_P + 2 * (size_t)nqb * TB * sizeof(float) + TB; }
-
-constexpr size_t TBWD_ALIAS_LDS = 4 * TILE_QKV + 2 * (size_t)TB * sizeof(float) + TB;
+constexpr size_t bwd_lds(int nqb, bool alias) {
+  return 4 * TILE_QKV + (alias ? 0 : TILE_P) + 2 * (size_t)nqb * TB * sizeof(float) + TB;
+}
 
 // One-block sequences (S <= 128: every training shape) take the aliased layout, two workgroups per CU.
 template <int NQB>
-int launch_bwd(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_mask, int B,
-               int S, int heads, int causal, void* dqkv, Drop drop, const int32_t* cu, hipStream_t s) {
+int launch_bwd(const AttnBwd& a) {
   constexpr bool ALIAS = NQB == 1;
-  constexpr size_t lds = ALIAS ? TBWD_ALIAS_LDS : tbwd_lds(NQB);
+  constexpr size_t lds = bwd_lds(NQB, ALIAS);
   static const hipError_t attr = hipFuncSetAttribute((const void*)attn_bwd_tiled_kernel<NQB, ALIAS>,
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (attr != hipSuccess) {
     set_error("attention (tiled backward): cannot raise dynamic LDS limit");
     return PGCA_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL((attn_bwd_tiled_kernel<NQB, ALIAS>), dim3(heads, B), dim3(TNT), lds, s, (const bf16_t*)qkv,
-                     (const bf16_t*)out, (const bf16_t*)dout, lse, key_mask, S, heads, causal, (bf16_t*)dqkv, drop, cu, S);
+  hipLaunchKernelGGL((attn_bwd_tiled_kernel<NQB, ALIAS>), dim3(a.heads, a.B), dim3(TNT), lds, a.stream, a);
   return check_launch("pgca_attention_bwd(tiled)");
 }
 
@@ -1039,19 +911,16 @@ int launch_bwd(const void* qkv, const void* out, const void* dout, const float* 
 
 namespace pgca {
 
-int attention_bwd_split(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_mask,
-                        int B, int S, int heads, int causal, void* dqkv, uint32_t drop_seed, uint32_t drop_threshold,
-                        float drop_scale, const int32_t* cu, void* stream) {
+int attention_bwd_split(const AttnBwd& a) {
+  constexpr size_t lds = bwd_lds(1, true);
   static const hipError_t attr = hipFuncSetAttribute((const void*)attn_bwd_split_kernel,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)TBWD_ALIAS_LDS);
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (attr != hipSuccess) {
     set_error("attention (split backward): cannot raise dynamic LDS limit");
     return PGCA_ERR_LAUNCH;
   }
-  const int nblk = (S + TB - 1) / TB;
-  hipLaunchKernelGGL(attn_bwd_split_kernel, dim3(heads, B, 2 * nblk), dim3(TNT), TBWD_ALIAS_LDS, (hipStream_t)stream,
-                     (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, key_mask, S, heads, causal,
-                     (bf16_t*)dqkv, Drop{drop_seed, drop_threshold, drop_scale}, cu, S);
+  const int nblk = (a.S + TB - 1) / TB;
+  hipLaunchKernelGGL(attn_bwd_split_kernel, dim3(a.heads, a.B, 2 * nblk), dim3(TNT), lds, a.stream, a);
   return check_launch("pgca_attention_bwd_split");
 }
 
@@ -1076,19 +945,14 @@ int attention_fwd_tiled(const void* qkv, const int32_t* key_mask, int B, int S, 
   return check_launch("pgca_attention_fwd(tiled)");
 }
 
-int attention_bwd_tiled(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* key_mask,
-                        int B, int S, int heads, int causal, void* dqkv, uint32_t drop_seed, uint32_t drop_threshold,
-                        float drop_scale, const int32_t* cu, void* stream) {
-  const Drop d{drop_seed, drop_threshold, drop_scale};
-  hipStream_t s = (hipStream_t)stream;
-  const int nqb = (S + TB - 1) / TB;
-  switch (nqb) {
-    case 1: return launch_bwd<1>(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, d, cu, s);
-    case 2: return launch_bwd<2>(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, d, cu, s);
-    case 3: return launch_bwd<3>(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, d, cu, s);
-    case 4: return launch_bwd<4>(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, d, cu, s);
+int attention_bwd_tiled(const AttnBwd& a) {
+  switch ((a.S + TB - 1) / TB) {
+    case 1: return launch_bwd<1>(a);
+    case 2: return launch_bwd<2>(a);
+    case 3: return launch_bwd<3>(a);
+    case 4: return launch_bwd<4>(a);
     default:
-      set_error("pgca_attention_bwd: S=%d exceeds the %d-token limit of the register-resident dQ accumulators", S,
+      set_error("pgca_attention_bwd: S=%d exceeds the %d-token limit of the register-resident dQ accumulators", a.S,
                 PGCA_ATTN_MAX_S);
       return PGCA_ERR_INVALID;
   }

@@ -125,4 +125,23 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* addr0, const unsi
   return __builtin_bit_cast(bf16x8, r);
 }
 
+// attention_tiled.hip's launchers behind the C entry points of attention.hip, which check the arguments.  The
+// backward's travel as one struct, from the entry point into the kernels.
+struct AttnBwd {
+  const bf16_t *qkv, *O, *dO;
+  const float* lse;
+  const int32_t* kmask;
+  int B, S, heads, causal;
+  bf16_t* dqkv;
+  Drop drop;
+  const int32_t* cu;
+  int Sp;  // the padded sequence length (geometry of key_mask, lse and the dropout index): see the forward kernel
+  hipStream_t stream;
+};
+int attention_fwd_tiled(const void* qkv, const int32_t* key_mask, int B, int S, int heads, int causal, void* out,
+                        float* lse, uint32_t drop_seed, uint32_t drop_threshold, float drop_scale, const int32_t* cu,
+                        void* stream);
+int attention_bwd_tiled(const AttnBwd& a);  // one pass, S <= PGCA_ATTN_MAX_S
+int attention_bwd_split(const AttnBwd& a);  // split by role, S <= PGCA_ATTN_SPLIT_MAX_S
+
 }  // namespace pgca

@@ -59,7 +59,7 @@ def test_split_backward_against_torch(hip, cfg):
 
 
 @pytest.mark.parametrize("cfg", [(2, 129, 1, True, 0.0), (2, 300, 2, False, 0.0), (2, 512, 1, True, 0.0),
-                                 (3, 256, 2, True, 0.1)],
+                                 (3, 256, 2, True, 0.1), (2, 300, 2, False, 0.1), (2, 385, 1, True, 0.1)],
                          ids=lambda c: f"B{c[0]}-S{c[1]}-h{c[2]}-{'causal' if c[3] else 'full'}-p{c[4]}")
 def test_split_backward_is_the_one_pass_arithmetic(hip, cfg):
     """dK / dV sum over the query blocks in ascending order, dQ adds a fresh partial per key block in ascending order, as
