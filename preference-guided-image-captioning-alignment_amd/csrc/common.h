@@ -32,14 +32,17 @@ __device__ __forceinline__ unsigned int pack2(float a, float b) {
   return __builtin_bit_cast(unsigned int, t);
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// xor-tree reductions over the 64 lanes of a wave (float, int, double): every lane returns the result
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));  // max(float, float) is fmaxf
   return v;
 }
 
@@ -112,6 +115,12 @@ struct Drop {
       mul2(base + 1u, m[1], m[2]);
       m[3] = mul(base + 3u);
     }
+  }
+  // v *= the multipliers of elements base .. base + 3
+  __device__ __forceinline__ void mask4(unsigned base, float4& v) const {
+    float m[4];
+    mul4(base, m);
+    v.x *= m[0]; v.y *= m[1]; v.z *= m[2]; v.w *= m[3];
   }
 };
 

@@ -4,7 +4,7 @@
 // per block in registers -> LDS -> one partial row per block (no atomics).
 #include <string.h>
 
-#include "common.h"
+#include "row_vec.h"
 
 using namespace pgca;
 
@@ -12,38 +12,37 @@ namespace {
 
 constexpr int MAXV = 8;  // float4 per lane -> H <= 2048
 
-struct RowVec {
-  float4 v[MAXV];
-};
+// The row layout of every wave-per-row kernel in this file: a row of H floats (H % 4 == 0) is held as NV float4 per
+// lane, and lane l owns columns 4 * (64 * j + l) .. + 3 of vector j, so vector j of the wave is 256 consecutive
+// columns (write_partials' LDS image and nv_for() rest on that).  col0(j, lane) is the first of those four columns;
+// for_cols calls f(j, c = col0) for the lane's vectors that start inside the row.
+// The loops of the two backward kernels that store or add to global memory are written out with col0 instead:
+// as for_cols lambdas they compile to more registers there, which costs some instantiations a wave per SIMD.
+__device__ __forceinline__ int col0(int j, int lane) { return (j * 64 + lane) * 4; }
+template <int NV, typename F>
+__device__ __forceinline__ void for_cols(int H, int lane, F&& f) {
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int c = col0(j, lane);
+    if (c < H) f(j, c);
+  }
+}
 
+// vectors past the end of the row read as zeros
 template <int NV>
 __device__ __forceinline__ void load_row_f32(const float* __restrict__ p, int H, int lane, float4 (&v)[NV]) {
 #pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = (j * 64 + lane) * 4;
-    v[j] = c < H ? *reinterpret_cast<const float4*>(p + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
+  for (int j = 0; j < NV; ++j) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for_cols<NV>(H, lane, [&](int j, int c) { v[j] = *reinterpret_cast<const float4*>(p + c); });
 }
 template <int NV>
 __device__ __forceinline__ void load_row_bf16(const bf16_t* __restrict__ p, int H, int lane, float4 (&v)[NV]) {
 #pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = (j * 64 + lane) * 4;
-    if (c < H) {
-      bf16x4 t = *reinterpret_cast<const bf16x4*>(p + c);
-      v[j] = make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
-    } else {
-      v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-}
-__device__ __forceinline__ void store_bf16x4(bf16_t* p, float4 v) {
-  bf16x4 t;
-  t[0] = (bf16_t)v.x;
-  t[1] = (bf16_t)v.y;
-  t[2] = (bf16_t)v.z;
-  t[3] = (bf16_t)v.w;
-  *reinterpret_cast<bf16x4*>(p) = t;
+  for (int j = 0; j < NV; ++j) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for_cols<NV>(H, lane, [&](int j, int c) {
+    bf16x4 t = *reinterpret_cast<const bf16x4*>(p + c);
+    v[j] = make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
+  });
 }
 
 template <int NV>
@@ -54,15 +53,40 @@ __device__ __forceinline__ void row_stats(const float4 (&v)[NV], int H, int lane
   for (int j = 0; j < NV; ++j) s += v[j].x + v[j].y + v[j].z + v[j].w;
   mean = wave_sum(s) / (float)H;
   float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = (j * 64 + lane) * 4;
-    if (c < H) {
-      const float a = v[j].x - mean, b = v[j].y - mean, cc = v[j].z - mean, d = v[j].w - mean;
-      q += a * a + b * b + cc * cc + d * d;
-    }
-  }
+  for_cols<NV>(H, lane, [&](int j, int) {
+    const float a = v[j].x - mean, b = v[j].y - mean, cc = v[j].z - mean, d = v[j].w - mean;
+    q += a * a + b * b + cc * cc + d * d;
+  });
   rstd = rsqrtf(wave_sum(q) / (float)H + eps);
+}
+
+// LayerNorm backward of one row.  In: xv the row of x, dy the gradient of the output, gm gamma.  Out: xv = x-hat,
+// dy = rstd * (g - mean(g) - xhat * mean(g * xhat)) with g = dy * gamma, the gradient of the input; dg / db
+// accumulate the row's dgamma / dbeta terms.
+template <int NV>
+__device__ __forceinline__ void ln_bwd_row(float4 (&xv)[NV], float4 (&dy)[NV], const float4 (&gm)[NV], float mean,
+                                           float rstd, int H, int lane, float4 (&dg)[NV], float4 (&db)[NV]) {
+  float c1 = 0.f, c2 = 0.f;
+  for_cols<NV>(H, lane, [&](int j, int) {
+    xv[j].x = (xv[j].x - mean) * rstd;
+    xv[j].y = (xv[j].y - mean) * rstd;
+    xv[j].z = (xv[j].z - mean) * rstd;
+    xv[j].w = (xv[j].w - mean) * rstd;
+    dg[j].x += dy[j].x * xv[j].x; dg[j].y += dy[j].y * xv[j].y;
+    dg[j].z += dy[j].z * xv[j].z; dg[j].w += dy[j].w * xv[j].w;
+    add4(db[j], dy[j]);
+    dy[j].x *= gm[j].x; dy[j].y *= gm[j].y; dy[j].z *= gm[j].z; dy[j].w *= gm[j].w;
+    c1 += dy[j].x + dy[j].y + dy[j].z + dy[j].w;
+    c2 += dy[j].x * xv[j].x + dy[j].y * xv[j].y + dy[j].z * xv[j].z + dy[j].w * xv[j].w;
+  });
+  c1 = wave_sum(c1) / (float)H;
+  c2 = wave_sum(c2) / (float)H;
+  for_cols<NV>(H, lane, [&](int j, int) {
+    dy[j].x = rstd * (dy[j].x - c1 - xv[j].x * c2);
+    dy[j].y = rstd * (dy[j].y - c1 - xv[j].y * c2);
+    dy[j].z = rstd * (dy[j].z - c1 - xv[j].z * c2);
+    dy[j].w = rstd * (dy[j].w - c1 - xv[j].w * c2);
+  });
 }
 
 // ------------------------------------------------------------------------------------ LN forward
@@ -84,21 +108,12 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     if (mean_o) mean_o[m] = mean;
     if (rstd_o) rstd_o[m] = rstd;
   }
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = (j * 64 + lane) * 4;
-    if (c < H) {
-      const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-      const float4 b = *reinterpret_cast<const float4*>(beta + c);
-      float4 y;
-      y.x = (v[j].x - mean) * rstd * g.x + b.x;
-      y.y = (v[j].y - mean) * rstd * g.y + b.y;
-      y.z = (v[j].z - mean) * rstd * g.z + b.z;
-      y.w = (v[j].w - mean) * rstd * g.w + b.w;
-      if (yf) *reinterpret_cast<float4*>(yf + (size_t)m * H + c) = y;
-      if (yb) store_bf16x4(yb + (size_t)m * H + c, y);
-    }
-  }
+  for_cols<NV>(H, lane, [&](int j, int c) {
+    const float4 y = ln_affine(v[j], mean, rstd, *reinterpret_cast<const float4*>(gamma + c),
+                               *reinterpret_cast<const float4*>(beta + c));
+    if (yf) *reinterpret_cast<float4*>(yf + (size_t)m * H + c) = y;
+    if (yb) store_bf16x4(yb + (size_t)m * H + c, y);
+  });
 }
 
 // ------------------------------------------------------------------------------------ LN backward
@@ -140,14 +155,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
   const int nw = gridDim.x * 4;
   float4 dg[NV], db[NV], gm[NV], sa[NV], sd[NV];
 #pragma unroll
-  for (int j = 0; j < NV; ++j) sa[j] = sd[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    dg[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    db[j] = dg[j];
-    const int c = (j * 64 + lane) * 4;
-    gm[j] = c < H ? *reinterpret_cast<const float4*>(gamma + c) : dg[j];
-  }
+  for (int j = 0; j < NV; ++j) dg[j] = db[j] = sa[j] = sd[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  load_row_f32<NV>(gamma, H, lane, gm);
   for (int m = wid; m < M; m += nw) {
     const size_t row = row_map ? (size_t)row_map[m] : (size_t)m;
     float4 xv[NV], dy[NV];
@@ -156,10 +165,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
       load_row_bf16<NV>(dyb + (size_t)m * H, H, lane, dy);
     else
       load_row_f32<NV>(dyf + (size_t)m * H, H, lane, dy);
-    // EXTRA (168 VGPRs, 3 waves/SIMD either way): the residual-stream gradient that joins here is requested with the row
-    // itself - one HBM round trip per row, not two; it is only consumed after the two wave reductions below
-    // (152 -> 128 us at 32768 x 1024).  Without EXTRA the 16 extra registers would cost a wave per SIMD (measured
-    // 95 -> 120 us), so that variant keeps the late load.
+    // EXTRA: the residual-stream gradient that joins here is requested with the row itself - one HBM round trip per
+    // row, not two; it is only consumed after the two wave reductions below (152 -> 128 us at 32768 x 1024).
+    // <4,true> compiles to 170 VGPRs, 2 waves/SIMD.  Without EXTRA (<4,false>: 118 VGPRs, 4 waves/SIMD) the 16
+    // extra registers would cost a wave per SIMD (measured 95 -> 120 us), so that variant keeps the late load.
     float4 av[EXTRA ? NV : 1];
     if constexpr (EXTRA) {
       if (add_to) load_row_f32<NV>(add_to + row * H, H, lane, av);
@@ -167,54 +176,26 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
     const float mean = mean_i[m], rstd = rstd_i[m];
     // packed token rows: the dropout hashes stay keyed on the token's position in the padded batch
     const unsigned drow = drop_rows ? (unsigned)drop_rows[row] : (unsigned)row;
-    float c1 = 0.f, c2 = 0.f;
+    ln_bwd_row<NV>(xv, dy, gm, mean, rstd, H, lane, dg, db);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-      const int c = (j * 64 + lane) * 4;
+      const int c = col0(j, lane);
       if (c < H) {
-        xv[j].x = (xv[j].x - mean) * rstd;
-        xv[j].y = (xv[j].y - mean) * rstd;
-        xv[j].z = (xv[j].z - mean) * rstd;
-        xv[j].w = (xv[j].w - mean) * rstd;
-        dg[j].x += dy[j].x * xv[j].x; dg[j].y += dy[j].y * xv[j].y;
-        dg[j].z += dy[j].z * xv[j].z; dg[j].w += dy[j].w * xv[j].w;
-        db[j].x += dy[j].x; db[j].y += dy[j].y; db[j].z += dy[j].z; db[j].w += dy[j].w;
-        dy[j].x *= gm[j].x; dy[j].y *= gm[j].y; dy[j].z *= gm[j].z; dy[j].w *= gm[j].w;
-        c1 += dy[j].x + dy[j].y + dy[j].z + dy[j].w;
-        c2 += dy[j].x * xv[j].x + dy[j].y * xv[j].y + dy[j].z * xv[j].z + dy[j].w * xv[j].w;
-      }
-    }
-    c1 = wave_sum(c1) / (float)H;
-    c2 = wave_sum(c2) / (float)H;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const int c = (j * 64 + lane) * 4;
-      if (c < H) {
-        float4 d;
-        d.x = rstd * (dy[j].x - c1 - xv[j].x * c2);
-        d.y = rstd * (dy[j].y - c1 - xv[j].y * c2);
-        d.z = rstd * (dy[j].z - c1 - xv[j].z * c2);
-        d.w = rstd * (dy[j].w - c1 - xv[j].w * c2);
+        float4 d = dy[j];
         const unsigned eidx = drow * (unsigned)H + (unsigned)c;
         if (add_to) {
           float4 a = EXTRA ? av[EXTRA ? j : 0] : *reinterpret_cast<const float4*>(add_to + row * H + c);
-          d.x += a.x; d.y += a.y; d.z += a.z; d.w += a.w;
+          add4(d, a);
           if (EXTRA) {
-            if (drop_add.on()) {  // bias gradient of the GEMM whose dropped output joined this stream
-              float m[4];
-              drop_add.mul4(eidx, m);
-              a.x *= m[0]; a.y *= m[1]; a.z *= m[2]; a.w *= m[3];
-            }
-            sa[j].x += a.x; sa[j].y += a.y; sa[j].z += a.z; sa[j].w += a.w;
+            // bias gradient of the GEMM whose dropped output joined this stream
+            if (drop_add.on()) drop_add.mask4(eidx, a);
+            add4(sa[j], a);
           }
         }
         *reinterpret_cast<float4*>(dx_out + row * H + c) = d;
-        if (drop_dx.on()) {  // the bf16 copy feeds the backward of a GEMM whose output was dropped: replay its mask
-          float m[4];
-          drop_dx.mul4(eidx, m);
-          d.x *= m[0]; d.y *= m[1]; d.z *= m[2]; d.w *= m[3];
-        }
-        if (EXTRA) { sd[j].x += d.x; sd[j].y += d.y; sd[j].z += d.z; sd[j].w += d.w; }
+        // the bf16 copy feeds the backward of a GEMM whose output was dropped: replay its mask
+        if (drop_dx.on()) drop_dx.mask4(eidx, d);
+        if (EXTRA) add4(sd[j], d);
         if (dx_bf) store_bf16x4(dx_bf + row * H + c, d);
       }
     }
@@ -251,9 +232,19 @@ __device__ __forceinline__ void add_head_terms(const XAttn& xa, int b, int s, in
       float4 t[NV];
       load_row_f32<NV>(xa.U + ((size_t)b * xa.heads + h) * H, H, lane, t);
 #pragma unroll
-      for (int j = 0; j < NV; ++j) { v[j].x += w * t[j].x; v[j].y += w * t[j].y; v[j].z += w * t[j].z; v[j].w += w * t[j].w; }
+      for (int j = 0; j < NV; ++j) fma4(v[j], w, t[j]);
     }
   }
+}
+// v += the attended row of sequence b (one vector per sequence: the `att` path above)
+template <int NV>
+__device__ __forceinline__ void add_att_row(const float* __restrict__ att, int b, int att_stride, int H, int lane,
+                                            float4 (&v)[NV]) {
+  if (!att) return;
+  float4 t[NV];
+  load_row_f32<NV>(att + (size_t)b * att_stride, H, lane, t);
+#pragma unroll
+  for (int j = 0; j < NV; ++j) add4(v[j], t[j]);
 }
 
 // ------------------------------------------------------------------------------------ embeddings
@@ -270,22 +261,16 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const long long* __restr
   if (orow >= n_rows) return;
   const int m = row_ids ? row_ids[orow] : orow;
   if (m < 0) {  // filler row of the packed layout: zeros (finite through every later kernel, zero gradient)
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const int c = (j * 64 + lane) * 4;
-      if (c < H) *reinterpret_cast<float4*>(h0 + (size_t)orow * H + c) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    for_cols<NV>(H, lane, [&](int, int c) {
+      *reinterpret_cast<float4*>(h0 + (size_t)orow * H + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+    });
     if (gamma && lane == 0) { mean_o[orow] = 0.f; rstd_o[orow] = 1.f; }
     return;
   }
   const int b = m / S, s = m % S;
   float4 v[NV], t[NV];
   load_row_f32<NV>(wte + (size_t)ids[m] * H, H, lane, v);
-  if (att) {
-    load_row_f32<NV>(att + (size_t)b * att_stride, H, lane, t);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) { v[j].x += t[j].x; v[j].y += t[j].y; v[j].z += t[j].z; v[j].w += t[j].w; }
-  }
+  add_att_row<NV>(att, b, att_stride, H, lane, v);
   add_head_terms<NV>(xa, b, s, S, H, lane, v);
   float mean = 0.f, rstd = 1.f;
   if (gamma) {
@@ -293,27 +278,16 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const long long* __restr
     if (lane == 0) { mean_o[orow] = mean; rstd_o[orow] = rstd; }
   }
   load_row_f32<NV>(wpe + (size_t)s * H, H, lane, t);
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int c = (j * 64 + lane) * 4;
-    if (c < H) {
-      float4 y = v[j];
-      if (gamma) {
-        const float4 g = *reinterpret_cast<const float4*>(gamma + c);
-        const float4 bb = *reinterpret_cast<const float4*>(beta + c);
-        y.x = (y.x - mean) * rstd * g.x + bb.x; y.y = (y.y - mean) * rstd * g.y + bb.y;
-        y.z = (y.z - mean) * rstd * g.z + bb.z; y.w = (y.w - mean) * rstd * g.w + bb.w;
-      }
-      y.x += t[j].x; y.y += t[j].y; y.z += t[j].z; y.w += t[j].w;
-      if (drop_e.on()) {  // GPT-2 embedding dropout (modeling_gpt2.py:604)
-        const unsigned e = (unsigned)m * (unsigned)H + (unsigned)c;
-        float m4[4];
-        drop_e.mul4(e, m4);
-        y.x *= m4[0]; y.y *= m4[1]; y.z *= m4[2]; y.w *= m4[3];
-      }
-      *reinterpret_cast<float4*>(h0 + (size_t)orow * H + c) = y;
-    }
-  }
+  for_cols<NV>(H, lane, [&](int j, int c) {
+    float4 y = v[j];
+    if (gamma)
+      y = ln_affine(y, mean, rstd, *reinterpret_cast<const float4*>(gamma + c),
+                    *reinterpret_cast<const float4*>(beta + c));
+    add4(y, t[j]);
+    // GPT-2 embedding dropout (modeling_gpt2.py:604)
+    if (drop_e.on()) drop_e.mask4((unsigned)m * (unsigned)H + (unsigned)c, y);
+    *reinterpret_cast<float4*>(h0 + (size_t)orow * H + c) = y;
+  });
 }
 
 __device__ __forceinline__ void atomic_add4(float* p, float4 d) {
@@ -345,12 +319,8 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
   float4 dg[NV], db[NV], gm[NV];
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    dg[j] = zero;
-    db[j] = zero;
-    const int c = (j * 64 + lane) * 4;
-    gm[j] = (gamma && c < H) ? *reinterpret_cast<const float4*>(gamma + c) : zero;
-  }
+  for (int j = 0; j < NV; ++j) dg[j] = db[j] = gm[j] = zero;
+  if (gamma) load_row_f32<NV>(gamma, H, lane, gm);
   const int nchunks = (B * S) / chunk;
   for (int ch = wid; ch < nchunks; ch += nw) {
     const int mbase = ch * chunk;
@@ -378,52 +348,21 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
       load_row_f32<NV>(g + pr * H, H, lane, dy);
       if (drop_e.on()) {
 #pragma unroll
-        for (int j = 0; j < NV; ++j) {
-          const unsigned e = (unsigned)m * (unsigned)H + (unsigned)((j * 64 + lane) * 4);
-          float m4[4];
-          drop_e.mul4(e, m4);
-          dy[j].x *= m4[0]; dy[j].y *= m4[1]; dy[j].z *= m4[2]; dy[j].w *= m4[3];
-        }
+        for (int j = 0; j < NV; ++j) drop_e.mask4((unsigned)m * (unsigned)H + (unsigned)col0(j, lane), dy[j]);
       }
       if (gamma) {
-        float4 xv[NV], t[NV];
+        float4 xv[NV];
         load_row_f32<NV>(wte + (size_t)id * H, H, lane, xv);
-        if (att) {
-          load_row_f32<NV>(att + (size_t)b * att_stride, H, lane, t);
-#pragma unroll
-          for (int j = 0; j < NV; ++j) { xv[j].x += t[j].x; xv[j].y += t[j].y; xv[j].z += t[j].z; xv[j].w += t[j].w; }
-        }
+        add_att_row<NV>(att, b, att_stride, H, lane, xv);
         add_head_terms<NV>(xa, b, s, S, H, lane, xv);
-        const float mean = mean_i[pr], rstd = rstd_i[pr];
-        float c1 = 0.f, c2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-          const int c = (j * 64 + lane) * 4;
-          if (c < H) {
-            xv[j].x = (xv[j].x - mean) * rstd; xv[j].y = (xv[j].y - mean) * rstd;
-            xv[j].z = (xv[j].z - mean) * rstd; xv[j].w = (xv[j].w - mean) * rstd;
-            dg[j].x += dy[j].x * xv[j].x; dg[j].y += dy[j].y * xv[j].y;
-            dg[j].z += dy[j].z * xv[j].z; dg[j].w += dy[j].w * xv[j].w;
-            db[j].x += dy[j].x; db[j].y += dy[j].y; db[j].z += dy[j].z; db[j].w += dy[j].w;
-            dy[j].x *= gm[j].x; dy[j].y *= gm[j].y; dy[j].z *= gm[j].z; dy[j].w *= gm[j].w;
-            c1 += dy[j].x + dy[j].y + dy[j].z + dy[j].w;
-            c2 += dy[j].x * xv[j].x + dy[j].y * xv[j].y + dy[j].z * xv[j].z + dy[j].w * xv[j].w;
-          }
-        }
-        c1 = wave_sum(c1) / (float)H;
-        c2 = wave_sum(c2) / (float)H;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-          dy[j].x = rstd * (dy[j].x - c1 - xv[j].x * c2); dy[j].y = rstd * (dy[j].y - c1 - xv[j].y * c2);
-          dy[j].z = rstd * (dy[j].z - c1 - xv[j].z * c2); dy[j].w = rstd * (dy[j].w - c1 - xv[j].w * c2);
-        }
+        ln_bwd_row<NV>(xv, dy, gm, mean_i[pr], rstd_i[pr], H, lane, dg, db);
       }
 #pragma unroll
       for (int j = 0; j < NV; ++j) {
-        const int c = (j * 64 + lane) * 4;
+        const int c = col0(j, lane);
         if (c < H) {
           atomic_add4(dwte + (size_t)id * H + c, dy[j]);
-          sa[j].x += dy[j].x; sa[j].y += dy[j].y; sa[j].z += dy[j].z; sa[j].w += dy[j].w;
+          add4(sa[j], dy[j]);
         }
       }
       if (xa.dU) {
@@ -433,9 +372,7 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
             if (h < xa.heads) {
               const float w = xa.w(b, h, s, S);
 #pragma unroll
-              for (int j = 0; j < NV; ++j) {
-                su[h][j].x += dy[j].x * w; su[h][j].y += dy[j].y * w; su[h][j].z += dy[j].z * w; su[h][j].w += dy[j].w * w;
-              }
+              for (int j = 0; j < NV; ++j) fma4(su[h][j], w, dy[j]);
             }
           }
         } else {
@@ -444,7 +381,7 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
             if (w != 0.f) {
 #pragma unroll
               for (int j = 0; j < NV; ++j) {
-                const int c = (j * 64 + lane) * 4;
+                const int c = col0(j, lane);
                 if (c < H)
                   atomic_add4(xa.dU + ((size_t)b * xa.heads + h) * H + c,
                               make_float4(dy[j].x * w, dy[j].y * w, dy[j].z * w, dy[j].w * w));
@@ -457,7 +394,7 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
     if (any) {
 #pragma unroll
       for (int j = 0; j < NV; ++j) {
-        const int c = (j * 64 + lane) * 4;
+        const int c = col0(j, lane);
         if (c < H) {
           if (datt) atomic_add4(datt + (size_t)b * H + c, sa[j]);
           if (ACCU && xa.dU) {
@@ -495,13 +432,8 @@ __global__ __launch_bounds__(256) void wpe_grad_kernel(const float* __restrict__
       pr = (size_t)(p0 + s);
     }
     float4 v = *reinterpret_cast<const float4*>(g + pr * H + c);
-    if (drop_e.on()) {
-      const unsigned e = (unsigned)m * (unsigned)H + (unsigned)c;
-      float m4[4];
-      drop_e.mul4(e, m4);
-      v.x *= m4[0]; v.y *= m4[1]; v.z *= m4[2]; v.w *= m4[3];
-    }
-    acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    if (drop_e.on()) drop_e.mask4((unsigned)m * (unsigned)H + (unsigned)c, v);
+    add4(acc, v);
   }
   atomic_add4(dwpe + (size_t)s * H + c, acc);
 }
@@ -509,27 +441,8 @@ __global__ __launch_bounds__(256) void wpe_grad_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------ column sums
 // out[c] (+)= sum_b part[b, c].  Block = 32 columns x 8 row slices: every load is 128 contiguous bytes,
 // each thread sums nparts/8 independent partials, the 8 slices meet in LDS.
-__global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restrict__ part, int nparts, int H,
-                                                            float* __restrict__ out, int accumulate) {
-  __shared__ float red[8][32];
-  const int cx = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cx;
-  float s = 0.f;
-  if (c < H) {
-#pragma unroll 4
-    for (int b = sl; b < nparts; b += 8) s += part[(size_t)b * H + c];
-  }
-  red[sl][cx] = s;
-  __syncthreads();
-  if (sl == 0 && c < H) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t += red[k][cx];
-    out[c] = accumulate ? out[c] + t : t;
-  }
-}
-
-// Up to four planes part[plane][b][c] folded into four outputs in one launch (blockIdx.y = plane).
+// Up to four planes part[plane][b][c] folded into four outputs in one launch (blockIdx.y = plane); pgca_colsum_finish
+// is the one-plane launch.
 __global__ __launch_bounds__(256) void colsum_finish4_kernel(const float* __restrict__ part, int nparts, int H,
                                                              float* o0, float* o1, float* o2, float* o3,
                                                              int accumulate) {
@@ -610,6 +523,25 @@ int nv_for(int H) { return (H + 255) / 256; }
     case 7: { constexpr int NV = 7; CALL; } break;   \
     default: { constexpr int NV = 8; CALL; } break;  \
   }
+#define DISPATCH_BOOL(COND, NAME, CALL)         \
+  if (COND) {                                   \
+    constexpr bool NAME = true;                 \
+    CALL;                                       \
+  } else {                                      \
+    constexpr bool NAME = false;                \
+    CALL;                                       \
+  }
+
+// d points at {seed, threshold, float bits of scale} (host memory) or is NULL
+static Drop drop_from_words(const uint32_t* d) {
+  Drop r{0u, 0u, 1.f};
+  if (d) {
+    r.seed = d[0];
+    r.threshold = d[1];
+    memcpy(&r.scale, &d[2], sizeof(float));
+  }
+  return r;
+}
 
 static int check_h(const char* who, int H) {
   if (H <= 0 || (H & 3) || H > MAXV * 256) {
@@ -653,26 +585,12 @@ extern "C" int pgca_layernorm_bwd(const void* dy_bf16, const float* dy_f32, cons
   dim3 grid(pgca_layernorm_bwd_blocks(M)), block(256);
   const int nv = nv_for(H);
   const size_t lds = (size_t)2 * 4 * nv * 256 * sizeof(float);
-  // drop_* point at {seed, threshold, float bits of scale} (host memory) or are NULL
-  auto mk = [](const uint32_t* d) {
-    Drop r{0u, 0u, 1.f};
-    if (d) {
-      r.seed = d[0];
-      r.threshold = d[1];
-      memcpy(&r.scale, &d[2], sizeof(float));
-    }
-    return r;
-  };
-  const Drop da = mk(drop_add), dd = mk(drop_dx);
-  if (part_extra) {
-    DISPATCH_NV(nv, hipLaunchKernelGGL((ln_bwd_kernel<NV, true>), grid, block, lds, s, (const bf16_t*)dy_bf16, dy_f32,
-                                       x, row_map, M, H, gamma, mean, rstd, add_to, dx_out, (bf16_t*)dx_bf16, part,
-                                       part_extra, da, dd, drop_rows));
-  } else {
-    DISPATCH_NV(nv, hipLaunchKernelGGL((ln_bwd_kernel<NV, false>), grid, block, lds, s, (const bf16_t*)dy_bf16, dy_f32,
-                                       x, row_map, M, H, gamma, mean, rstd, add_to, dx_out, (bf16_t*)dx_bf16, part,
-                                       part_extra, da, dd, drop_rows));
-  }
+  const Drop da = drop_from_words(drop_add), dd = drop_from_words(drop_dx);
+  DISPATCH_BOOL(part_extra != nullptr, EXTRA,
+                DISPATCH_NV(nv, hipLaunchKernelGGL((ln_bwd_kernel<NV, EXTRA>), grid, block, lds, s,
+                                                   (const bf16_t*)dy_bf16, dy_f32, x, row_map, M, H, gamma, mean, rstd,
+                                                   add_to, dx_out, (bf16_t*)dx_bf16, part, part_extra, da, dd,
+                                                   drop_rows)));
   return check_launch("pgca_layernorm_bwd");
 }
 
@@ -682,8 +600,8 @@ extern "C" int pgca_colsum_finish(const float* part, int32_t nparts, int32_t H, 
     set_error("pgca_colsum_finish: bad arguments");
     return PGCA_ERR_INVALID;
   }
-  hipLaunchKernelGGL(colsum_finish_kernel, dim3((H + 31) / 32), dim3(256), 0, (hipStream_t)stream, part, nparts, H,
-                     out, accumulate);
+  hipLaunchKernelGGL(colsum_finish4_kernel, dim3((H + 31) / 32, 1), dim3(256), 0, (hipStream_t)stream, part, nparts, H,
+                     out, (float*)nullptr, (float*)nullptr, (float*)nullptr, accumulate);
   return check_launch("pgca_colsum_finish");
 }
 
@@ -716,16 +634,6 @@ extern "C" int pgca_colsum(const void* x_bf16, const float* x_f32, int32_t M, in
   hipLaunchKernelGGL(colsum_kernel, grid, block, 0, (hipStream_t)stream, (const bf16_t*)x_bf16, x_f32, M, N, ld, rows,
                      part);
   return check_launch("pgca_colsum");
-}
-
-static Drop drop_from_words(const uint32_t* d) {
-  Drop r{0u, 0u, 1.f};
-  if (d) {
-    r.seed = d[0];
-    r.threshold = d[1];
-    memcpy(&r.scale, &d[2], sizeof(float));
-  }
-  return r;
 }
 
 extern "C" int pgca_embed_fwd(const int64_t* ids, int32_t B, int32_t S, int32_t H, const float* wte, const float* wpe,
@@ -780,15 +688,12 @@ extern "C" int pgca_embed_bwd(const float* g, const int64_t* ids, const int32_t*
   const XAttn xa{U, dU, xheads, drop_from_words(drop_x)};
   const Drop de = drop_from_words(drop_e);
   const int chunk = embed_chunk(S);
-  if (nv <= 4 && xheads <= 8) {
-    DISPATCH_NV(nv, hipLaunchKernelGGL((embed_bwd_kernel<(NV <= 4 ? NV : 4), true>), grid, block, lds, s, g,
-                                       (const long long*)ids, row_mask, B, S, H, wte, attended, gamma, mean, rstd, dwte,
-                                       dattended, part, att_stride, xa, de, chunk, cu_seqlens));
-  } else {
-    DISPATCH_NV(nv, hipLaunchKernelGGL((embed_bwd_kernel<NV, false>), grid, block, lds, s, g, (const long long*)ids,
-                                       row_mask, B, S, H, wte, attended, gamma, mean, rstd, dwte, dattended, part,
-                                       att_stride, xa, de, chunk, cu_seqlens));
-  }
+  // ACCU is only taken (and only instantiated) for nv <= 4
+  DISPATCH_BOOL(nv <= 4 && xheads <= 8, ACCU,
+                DISPATCH_NV(nv, hipLaunchKernelGGL((embed_bwd_kernel<(ACCU && NV > 4 ? 4 : NV), ACCU>), grid, block, lds,
+                                                   s, g, (const long long*)ids, row_mask, B, S, H, wte, attended, gamma,
+                                                   mean, rstd, dwte, dattended, part, att_stride, xa, de, chunk,
+                                                   cu_seqlens)));
   {
     const int nthr = S * (H >> 2);
     int ys = B >= 64 ? 8 : (B >= 8 ? 2 : 1);

@@ -1,10 +1,20 @@
 // Small HBM-bound kernels of the step: ViT patch gather, sequence reduce + DPO loss,
 // masked mean pool, L2 normalise, NT-Xent scalar reduce, fused clip/AdamW over flat buffers.
-#include "common.h"
+#include "row_vec.h"
 
 using namespace pgca;
 
 namespace {
+
+// Sum of v over a block of four waves, returned to every thread: wave reduce, lane 0 of each wave writes red[wave],
+// barrier, add the four.  Every thread of the block must call it; red is 4 elements of LDS this call owns.
+template <typename T>
+__device__ __forceinline__ T block_sum4(T v, T* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
 
 // ------------------------------------------------------------------------------------ ViT input
 // out[(b*G*G + gy*G + gx), c*P*P + ky*P + kx] = pixels[b, c, gy*P+ky, gx*P+kx]   (bf16)
@@ -18,9 +28,7 @@ __global__ void patchify_kernel(const float* __restrict__ px, int B, int I, int 
     const int c = col / (P * P), ky = (col / P) % P, kx = col % P;
     const int b = (int)(row / (G * G)), gy = (int)(row / G) % G, gx = (int)(row % G);
     const float4 v = *reinterpret_cast<const float4*>(px + (((size_t)b * 3 + c) * I + gy * P + ky) * I + gx * P + kx);
-    bf16x4 t;
-    t[0] = (bf16_t)v.x; t[1] = (bf16_t)v.y; t[2] = (bf16_t)v.z; t[3] = (bf16_t)v.w;
-    *reinterpret_cast<bf16x4*>(out + e) = t;
+    store_bf16x4(out + e, v);
   }
 }
 
@@ -88,8 +96,7 @@ __global__ void seq_reduce_kernel(const float* __restrict__ tok, const int* __re
     // 64 lanes wide) - O(nseq + count) per wave instead of a scan over every row of the batch
     int before = 0;
     for (int i = lane; i < q; i += 64) before += seq_count[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
+    before = wave_sum(before);
     const int n = seq_count[q];
     for (int r = lane; r < n; r += 64) s += tok[before + r];
   } else {
@@ -135,6 +142,7 @@ __global__ void dpo_loss_kernel(const float* __restrict__ pw, const float* __res
     a_w += pw[i];
     a_l += pl[i];
   }
+  // five sums behind one barrier, finished by five threads: not block_sum4, which would take a barrier per sum
   float v[5] = {a_loss, a_margin, a_acc, a_w, a_l};
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
@@ -183,8 +191,7 @@ __global__ void seq_counts_kernel(const long long* __restrict__ mask, int Bq, in
     if (mask32) mask32[(size_t)b * S + t] = m;
     if (t >= 1) c += m;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  c = wave_sum(c);
   if (lane == 0) counts[b] = c;
 }
 __global__ void seq_compact_kernel(const long long* __restrict__ ids, const long long* __restrict__ mask,
@@ -196,8 +203,7 @@ __global__ void seq_compact_kernel(const long long* __restrict__ ids, const long
   if (b >= Bq) return;
   int off = 0;  // exclusive prefix of the counts: Bq <= a few hundred, every wave sums its own
   for (int i = lane; i < b; i += 64) off += counts[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) off += __shfl_xor(off, o);
+  off = wave_sum(off);
   if (b == Bq - 1 && lane == 0) n_rows[0] = off + counts[b];
   for (int t0 = 0; t0 < S - 1; t0 += 64) {
     const int t = t0 + lane;
@@ -221,8 +227,7 @@ __global__ void seq_lens_kernel(const int* __restrict__ mask32, int Bq, int S, i
   int len = 0;
   for (int t = lane; t < S; t += 64)
     if (mask32[(size_t)b * S + t] != 0) len = t + 1;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) len = max(len, __shfl_xor(len, o));
+  len = wave_max(len);
   if (lane == 0) lens[b] = len;
 }
 // One wave per sequence (+ one for the filler tail, b == Bq): offsets, row ids, the filler, and the compact rows' map.
@@ -237,11 +242,8 @@ __global__ void seq_pack_kernel(const int* __restrict__ lens, int Bq, int S, int
     off += lens[i];
     if (counts) coff += counts[i];
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    off += __shfl_xor(off, o);
-    coff += __shfl_xor(coff, o);
-  }
+  off = wave_sum(off);
+  coff = wave_sum(coff);
   if (b == Bq) {  // filler: rows off .. padded-1, as F unmasked pseudo-sequences of at most S rows each
     const int padded = (off + pad_to - 1) / pad_to * pad_to;
     const int F = (pad_to - 1 + S - 1) / S;
@@ -324,10 +326,8 @@ __global__ void ntxent_loss_kernel(const float* __restrict__ lr, const float* __
   __shared__ float red[4];
   float s = 0.f;
   for (int i = threadIdx.x; i < n_local; i += blockDim.x) s += (lr[i] - diag[i]) + (lc[i] - diag[i]);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) loss[0] = (red[0] + red[1] + red[2] + red[3]) / (2.f * (float)n_total);
+  s = block_sum4(s, red);
+  if (threadIdx.x == 0) loss[0] = s / (2.f * (float)n_total);
 }
 
 // ------------------------------------------------------------------------------------ optimiser
@@ -347,26 +347,25 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g
       for (long long k = e; k < n && k < e + 4; ++k) s += g[k] * g[k];
     }
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  s = block_sum4(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// sqrt(grad_scale^2 * sum of the sqnorm partials), summed in double (shuffles on the 64-bit value: a wave reduce in
+// double via two floats is lossy); single block of 256 threads, every thread returns the norm
+__device__ __forceinline__ float partials_norm(const float* __restrict__ part, int nparts, float grad_scale,
+                                               double* red) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += blockDim.x) s += (double)part[i];
+  return (float)sqrt(block_sum4(s, red) * (double)grad_scale * (double)grad_scale);
 }
 
 __global__ void step_control_kernel(const float* __restrict__ part, int nparts, float max_norm, float base_lr,
                                     int warmup, int total_steps, int sched_stride, float beta1, float beta2,
                                     float grad_scale, const float* __restrict__ gate, float* __restrict__ ctrl) {
   __shared__ double red[4];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) s += (double)part[i];
-  // wave reduce in double via two floats is lossy; use shuffles on the 64-bit value
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
+  const float norm = partials_norm(part, nparts, grad_scale, red);
   if (threadIdx.x == 0) {
-    const double tot = (red[0] + red[1] + red[2] + red[3]) * (double)grad_scale * (double)grad_scale;
-    const float norm = (float)sqrt(tot);
     // `gate` (optional): the loss of the micro-batch that closes the accumulation group.  The reference drops the whole
     // group without stepping when THAT loss is non-finite (its zero_grad() is only real on the boundary micro-step,
     // trainer.py:481-489 under accelerate's accumulate()).
@@ -401,14 +400,8 @@ __global__ void step_control_kernel(const float* __restrict__ part, int nparts, 
 // 619-623): coef[0] = min(1, max_norm / (norm + 1e-6)), norm from the sqnorm partials; then scale_dev multiplies.
 __global__ void clip_coef_kernel(const float* __restrict__ part, int nparts, float max_norm, float* __restrict__ coef) {
   __shared__ double red[4];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) s += (double)part[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
+  const float norm = partials_norm(part, nparts, 1.f, red);
   if (threadIdx.x == 0) {
-    const float norm = (float)sqrt(red[0] + red[1] + red[2] + red[3]);
     coef[0] = isfinite(norm) ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;  // NaN gradients are left for the step's check
     coef[1] = norm;
   }
@@ -465,9 +458,7 @@ __global__ void cast_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict
   for (long long e = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; e < n; e += stride) {
     if (e + 4 <= n) {
       const float4 v = *reinterpret_cast<const float4*>(x + e);
-      bf16x4 t;
-      t[0] = (bf16_t)v.x; t[1] = (bf16_t)v.y; t[2] = (bf16_t)v.z; t[3] = (bf16_t)v.w;
-      *reinterpret_cast<bf16x4*>(y + e) = t;
+      store_bf16x4(y + e, v);
     } else {
       for (long long k = e; k < n; ++k) y[k] = (bf16_t)x[k];
     }

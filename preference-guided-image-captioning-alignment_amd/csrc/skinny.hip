@@ -13,7 +13,7 @@
 //          / gelu_new / f32 residual, writes the f32 and/or bf16 result (arbitrary row strides: the K/V cache row, the
 //          residual stream) and optionally runs the NEXT LayerNorm on the finished row (its bf16 output is the next
 //          product's operand: no separate LN launch).
-#include "common.h"
+#include "row_vec.h"
 
 using namespace pgca;
 
@@ -127,11 +127,7 @@ __global__ __launch_bounds__(256) void skinny_finish_kernel(const float* __restr
         v[i].x += r.x; v[i].y += r.y; v[i].z += r.z; v[i].w += r.w;
       }
       if (out_f32) *reinterpret_cast<float4*>(out_f32 + (size_t)m * ld_out_f32 + c) = v[i];
-      if (out_bf16) {
-        bf16x4 o;
-        o[0] = f2bf(v[i].x); o[1] = f2bf(v[i].y); o[2] = f2bf(v[i].z); o[3] = f2bf(v[i].w);
-        *reinterpret_cast<bf16x4*>(out_bf16 + (size_t)m * ld_out_bf16 + c) = o;
-      }
+      if (out_bf16) store_bf16x4(out_bf16 + (size_t)m * ld_out_bf16 + c, v[i]);
       s += v[i].x + v[i].y + v[i].z + v[i].w;
     }
   }
@@ -160,12 +156,7 @@ __global__ __launch_bounds__(256) void skinny_finish_kernel(const float* __restr
     if (c < N) {
       const float4 g = *reinterpret_cast<const float4*>(ln_gamma + c);
       const float4 b = *reinterpret_cast<const float4*>(ln_beta + c);
-      bf16x4 o;
-      o[0] = f2bf((v[i].x - mean) * rstd * g.x + b.x);
-      o[1] = f2bf((v[i].y - mean) * rstd * g.y + b.y);
-      o[2] = f2bf((v[i].z - mean) * rstd * g.z + b.z);
-      o[3] = f2bf((v[i].w - mean) * rstd * g.w + b.w);
-      *reinterpret_cast<bf16x4*>(ln_out + (size_t)m * ld_ln + c) = o;
+      store_bf16x4(ln_out + (size_t)m * ld_ln + c, ln_affine(v[i], mean, rstd, g, b));
     }
   }
 }

@@ -237,6 +237,12 @@ def test_colsum(hip):
     hip.colsum(M, N, N, part, x_f32=x)
     hip.colsum_finish(part, nb, N, out)
     close(out, x.sum(0), 1e-5, "colsum f32")
+    # three planes into three outputs in one launch (the fourth output is NULL), added to what the outputs hold
+    part3 = rnd(3, nb, N, seed=2)
+    outs = [torch.ones(N, device=dev()) for _ in range(3)]
+    hip.colsum_finish4(part3, 3, nb, N, outs, accumulate=True)
+    for k in range(3):
+        close(outs[k], part3[k].sum(0) + 1, 1e-5, f"colsum_finish4 plane {k}")
 
 
 def attn_ref(qkv, mask, B, S, heads, causal):
@@ -590,8 +596,10 @@ def test_attention_dropout_fwd_bwd(hip):
     close(dqkv, x.grad, 1.0 / 40, "attn bwd with replayed dropout")
 
 
-def test_layernorm_bwd_replays_neighbour_dropout(hip):
-    M, H = 50, 256
+@pytest.mark.parametrize("H", [256, 320, 1600])
+def test_layernorm_bwd_replays_neighbour_dropout(hip, H):
+    """H = 320: two vectors per lane with a partly filled last one; H = 1600: seven, lanes 0-15 live in the last."""
+    M = 50
     x, dy, add = rnd(M, H, seed=1), rnd(M, H, seed=2), rnd(M, H, seed=3)
     gamma = rnd(H, seed=4) * 0.1 + 1
     mean, rstd = torch.zeros(M, device=dev()), torch.zeros(M, device=dev())
@@ -614,8 +622,10 @@ def test_layernorm_bwd_replays_neighbour_dropout(hip):
     close(sd, (want * md).sum(0), 2e-5, "masked column sum of dx")
 
 
-def test_embed_train_mode_heads_and_dropout(hip):
-    B, S, H, V, XH = 3, 9, 128, 50, 8
+@pytest.mark.parametrize("XH", [8, 12])
+def test_embed_train_mode_heads_and_dropout(hip, XH):
+    """XH = 12 takes the per-row dU atomics (more than the 8 heads the kernel accumulates in registers)."""
+    B, S, H, V = 3, 9, 128, 50
     ids = torch.randint(0, V, (B, S), generator=torch.Generator().manual_seed(0)).to(dev())
     wte, wpe = rnd(V, H, seed=1), rnd(16, H, seed=2)
     U, bo = rnd(B, XH, H, seed=3), rnd(H, seed=4)
