@@ -1,18 +1,25 @@
-// bf16 MFMA GEMM for gfx950 (MI355X): C[M,N] = epilogue(alpha * A·B + bias).
+// bf16 MFMA GEMM for gfx950 (MI355X): C[M,N] = epilogue(alpha * A·B + bias).  This file holds the planner, the C entry
+// points and two of the kernel families; the third (phase-staggered 256^2) is gemm_phase.hip / gemm_pair.hip.
 //
-// One kernel template serves the three operand layouts of the hot path (pgca_hip.h):
+// Every kernel serves the three operand layouts of the hot path (pgca_hip.h):
 //   NT  A[M,K] · B[N,K]^t   both operands contiguous along K   -> ds_read_b128 fragments
 //   NN  A[M,K] · B[K,N]     B strided along K                  -> ds_read_b64_tr_b16 fragments
 //   TN  A[K,M]^t · B[K,N]   both strided along K (wgrad X^t dY) -> ds_read_b64_tr_b16 fragments
 // so forward, dgrad and wgrad all read the reference's native weight layouts
 // (Conv1D [in,out], nn.Linear [out,in]) from ONE bf16 mirror - no transposed copies.
 //
-// Geometry: 128x128 block tile, BK = 64, 256 threads = 4 waves (2x2), each wave 64x64 =
-// 4x4 MFMA 16x16x32 accumulators.  Global -> VGPR (buffer loads, OOB lanes read 0) -> LDS
-// (XOR-swizzled, conflict-free for both fragment read kinds), double-buffered: the next
-// tile's global loads are issued before the current tile's MFMAs and written to the other
-// LDS buffer after them (one barrier per K tile).
-#include <atomic>
+//   gemm_kernel              128x128 tile, BK = 64, 4 waves (2x2): any shape; the small and the K-unaligned problems.
+//                            Global -> VGPR (buffer loads, OOB lanes read 0) -> LDS (XOR-swizzled, conflict-free for
+//                            both fragment read kinds), double-buffered: the next tile's global loads are issued before
+//                            the current tile's MFMAs and written to the other LDS buffer after them (one barrier per
+//                            K tile).
+//   gemm256_kernel           256x256 tile, BK = 64, 8 waves (2x4), operands by LDS-DMA, 2 stages; split-K for the
+//                            weight gradients (schedule 0: the TN layout).
+//   gemm256_group_tn_kernel  up to four TN problems as one grid of that tile.
+//   gemm256s_kernel / gemm256s_pair_kernel (gemm_phase.hip, gemm_pair.hip)  the same tile with a phase-staggered
+//                            4-stage BK = 32 loop (schedule 6: NT and NN).
+// plan_gemm chooses among them; every kernel ends in run_epilogue (gemm_epilogue.h) per 64 x 64 accumulator block and
+// orders its tiles with xcd_remap + group_m_tile (gemm_device.h).
 #include <string>
 
 #include "gemm_device.h"
@@ -23,23 +30,8 @@ template <int LA, int LB>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const pgca_gemm_args a, int ntm, int ntn) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2][2][TILE_BYTES];
 
-  // XCD-aware tile order: blocks that share an XCD (bid % 8) walk a contiguous run of tiles,
-  // M fastest, so an XCD's resident blocks share B panels in its private L2.
-  const int nwg = ntm * ntn;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  // ... and inside that run tiles are visited in 8-row groups, N fastest within a group: the ~64 blocks an
-  // XCD holds at once cover an 8 x 8 patch of tiles, so each A and B panel is fetched into its L2 once per 8 uses.
-  constexpr int GROUP_M = 8;
-  const int per_group = GROUP_M * ntn;
-  const int group = bid / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsize = min(GROUP_M, ntm - first_m);
-  const int in_group = bid - group * per_group;
-  const int tm = first_m + in_group % gsize, tn = in_group / gsize;
+  int tm, tn;
+  group_m_tile(xcd_remap(blockIdx.x, ntm * ntn), ntm, ntn, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
 
   const int t = threadIdx.x;
@@ -102,22 +94,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const pgca_gemm_args a, in
   }
 
   // ------------------------------------------------------------------------------- epilogue
-  unsigned char* sbase = &smem[0][0][0];
-  switch (a.epilogue) {
-    case PGCA_EPI_ROWSTATS: epilogue_rowstats(a, acc, m0, n0, tn, wm, wn, lane); break;
-    case PGCA_EPI_GELU_NEW: epilogue_store<PGCA_EPI_GELU_NEW>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    case PGCA_EPI_QUICK_GELU: epilogue_store<PGCA_EPI_QUICK_GELU>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    case PGCA_EPI_RELU: epilogue_store<PGCA_EPI_RELU>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    case PGCA_EPI_TANH: epilogue_store<PGCA_EPI_TANH>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    case PGCA_EPI_DGELU_NEW: epilogue_store<PGCA_EPI_DGELU_NEW>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    case PGCA_EPI_DRELU: epilogue_store<PGCA_EPI_DRELU>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    case PGCA_EPI_DTANH: epilogue_store<PGCA_EPI_DTANH>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    case PGCA_EPI_DLOGITS: epilogue_store<PGCA_EPI_DLOGITS>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    case PGCA_EPI_DQUICK_GELU: epilogue_store<PGCA_EPI_DQUICK_GELU>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    case PGCA_EPI_GELU_NEW_D: epilogue_store<PGCA_EPI_GELU_NEW_D>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    case PGCA_EPI_MUL_AUX: epilogue_store<PGCA_EPI_MUL_AUX>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-    default: epilogue_store<PGCA_EPI_NONE>(a, acc, sbase, m0, n0, wm, wn, lane, wave); break;
-  }
+  run_epilogue(a, acc, &smem[0][0][0], m0 + wm * 64, n0 + wn * 64, lane, wave);
 }
 
 __global__ void rowstats_combine_kernel(const float* __restrict__ smax, const float* __restrict__ ssum, int stat_ld,
@@ -157,25 +134,12 @@ __global__ void rowstats_combine_kernel(const float* __restrict__ smax, const fl
 template <int LA, int LB, bool RAW = false>
 __device__ __forceinline__ void gemm256_body(const pgca_gemm_args& a, int ntm, int ntn, int nk_per_split, int bid_in,
                                              int ksplit, unsigned char* smem2) {  // smem2: [2 stages][A | B][32 KiB]
-  const int nwg = ntm * ntn;
-  int bid = bid_in;
   int tm, tn;
   if (RAW) {
-    tm = bid / ntn;
-    tn = bid - tm * ntn;
+    tm = bid_in / ntn;
+    tn = bid_in - tm * ntn;
   } else {
-    {
-      const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-      bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    constexpr int GROUP_M = 8;
-    const int per_group = GROUP_M * ntn;
-    const int group = bid / per_group;
-    const int first_m = group * GROUP_M;
-    const int gsize = min(GROUP_M, ntm - first_m);
-    const int in_group = bid - group * per_group;
-    tm = first_m + in_group % gsize;
-    tn = in_group / gsize;
+    group_m_tile(xcd_remap(bid_in, ntm * ntn), ntm, ntn, tm, tn);
   }
   const int m0 = tm * BM2, n0 = tn * BN2;
 
@@ -186,12 +150,11 @@ __device__ __forceinline__ void gemm256_body(const pgca_gemm_args& a, int ntm, i
 
   const bf16_t* A = reinterpret_cast<const bf16_t*>(a.A);
   const bf16_t* B = reinterpret_cast<const bf16_t*>(a.B);
-  const int nrows_b = a.epilogue == PGCA_EPI_DLOGITS ? a.N : a.N;
 
-  Dma<LA> da;
-  Dma<LB> db;
+  Dma<LA, BK> da;
+  Dma<LB, BK> db;
   da.init(lane, wave, a.lda, m0, LA == 0 ? a.M : ((a.M + 7) & ~7));
-  db.init(lane, wave, a.ldb, n0, LB == 0 ? nrows_b : ((nrows_b + 7) & ~7));
+  db.init(lane, wave, a.ldb, n0, LB == 0 ? a.N : ((a.N + 7) & ~7));
   const bf16_t* abase = LA == 0 ? A + (size_t)m0 * a.lda : A + m0;
   const bf16_t* bbase = LB == 0 ? B + (size_t)n0 * a.ldb : B + n0;
   const size_t astep = LA == 0 ? (size_t)BK : (size_t)BK * a.lda;
@@ -212,15 +175,13 @@ __device__ __forceinline__ void gemm256_body(const pgca_gemm_args& a, int ntm, i
   bbase += (size_t)kt0 * bstep;
 #ifdef PGCA_GEMM_TIMING
   unsigned long long ts0, ts1, ts2, ts3;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts0)::"memory");
 #endif
+  TSTAMP(ts0);
   da.issue(abase, smem2, wave);
   db.issue(bbase, smem2 + TILE2_BYTES, wave);
   dma_wait();
   __syncthreads();
-#ifdef PGCA_GEMM_TIMING
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts1)::"memory");
-#endif
+  TSTAMP(ts1);
 
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
@@ -243,13 +204,12 @@ __device__ __forceinline__ void gemm256_body(const pgca_gemm_args& a, int ntm, i
     __syncthreads();  // ... and every wave is done reading tile kt
   }
 
+  TSTAMP(ts2);
+  run_epilogue(a, acc[0], smem2, m0 + wm * 128, n0 + wn * 64, lane, wave);
+  run_epilogue(a, acc[1], smem2, m0 + wm * 128 + 64, n0 + wn * 64, lane, wave);
 #ifdef PGCA_GEMM_TIMING
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts2)::"memory");
-#endif
-  run_epilogue(a, acc[0], smem2, m0 + wm * 128, n0, tn, wn, lane, wave);
-  run_epilogue(a, acc[1], smem2, m0 + wm * 128 + 64, n0, tn, wn, lane, wave);
-#ifdef PGCA_GEMM_TIMING
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts3)::"memory");
+  dma_wait();  // the stores have left
+  TSTAMP(ts3);
   if (a.stat_max && a.epilogue != PGCA_EPI_ROWSTATS && lane == 0) {
     float* o = a.stat_max + ((size_t)blockIdx.x * 8 + wave) * 8;
     o[0] = (float)(ts1 - ts0); o[1] = (float)(ts2 - ts1); o[2] = (float)(ts3 - ts2); o[3] = (float)nk;
@@ -279,12 +239,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_group_tn_kernel(const pgca_gro
   // after problem with the SHORTER tile dimension running fastest, and XCD x takes a contiguous run of that order - a
   // compact rectangle of (mostly) one problem, so the 24 tiles an XCD holds for a GPT-2-M block stream ~11 operand panels
   // through its L2 instead of ~24 when every problem is spread over all eight XCDs.
-  int b;
-  {
-    const int total = gp.start[4];
-    const int xcd = blockIdx.x & 7, q = total >> 3, r = total & 7;
-    b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-  }
+  const int b = xcd_remap(blockIdx.x, gp.start[4]);
   int p = 0;
   if (b >= gp.start[1]) p = 1;
   if (b >= gp.start[2]) p = 2;
@@ -324,62 +279,19 @@ __global__ __launch_bounds__(512, 2) void gemm256_group_tn_kernel(const pgca_gro
 
 constexpr size_t GEMM256_LDS = 4 * TILE2_BYTES;  // 128 KiB
 
-int ensure_gemm256_attr() {
-  static std::atomic<int> done{0};
-  if (!done.load(std::memory_order_acquire)) {
-    hipError_t e1 = hipFuncSetAttribute((const void*)gemm256_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)GEMM256_LDS);
-    hipError_t e2 = hipFuncSetAttribute((const void*)gemm256_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)GEMM256_LDS);
-    hipError_t e3 = hipFuncSetAttribute((const void*)gemm256_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)GEMM256_LDS);
-    hipError_t e4 = hipFuncSetAttribute((const void*)gemm256_group_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)GEMM256_LDS);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("gemm256: cannot raise dynamic LDS limit");
-      return PGCA_ERR_LAUNCH;
-    }
-    done.store(1, std::memory_order_release);  // idempotent: a racing second caller only repeats the same calls
-  }
-  return PGCA_OK;
-}
-
-// Kernel choice: big, K-aligned problems take the 256^2 LDS-DMA kernel, everything else the general 128^2
-// one.  Gradient-accumulating GEMMs with few output tiles but a long K (weight gradients: K = tokens) are split
-// along K so the 256^2 kernel still fills the chip; partials meet through f32 atomics.
-int plan_tile(const pgca_gemm_args& a, int* splits_out) {
-  const int ncols = a.epilogue == PGCA_EPI_DLOGITS ? a.out_cols : a.N;
-  const int ntm2 = (a.M + BM2 - 1) / BM2, ntn2 = (ncols + BN2 - 1) / BN2;
-  const int force = gemm_tuning().tile;
-  const int nk_total = a.K / BK;
-  int splits = 1;
-  const bool splittable = a.epilogue == PGCA_EPI_NONE && a.accumulate && a.out_f32 && !a.out_bf16 && !a.bias &&
-                          !a.residual;
-  if (splittable && ntm2 * ntn2 < 192) {
-    splits = 256 / (ntm2 * ntn2);
-    if (splits > nk_total / 8) splits = nk_total / 8;
-    if (splits > 16) splits = 16;
-    if (splits < 1) splits = 1;
-  }
-  const bool want256 = force ? force == 256 : (ntm2 * ntn2 * splits >= 192);
-  *splits_out = splits;
-  return ((a.K % BK) == 0 && want256 && a.M >= 8 && ncols >= 8) ? 256 : 128;
-}
-
-}  // namespace
-
 // Schedule of the 256^2 tile: 0 = gemm256_kernel (2-stage BK=64 loop), 6 = gemm256s_kernel (gemm_phase.hip: phase-staggered
 // wave groups, 4-stage BK=32 ring).  Schedules that did not pay (BK=32 ring with plain barriers, phased halves, a 4-wave
 // 128x128-per-wave asm pipeline, a 256x128 two-workgroups-per-CU tile) were measured, documented in DESIGN.md section 5 and
 // removed from the library.
-static int plan_variant(const pgca_gemm_args& a) {
+int plan_variant(const pgca_gemm_args& a) {
   const int forced = gemm_tuning().schedule;
   if (forced >= 0) return forced == 6 ? 6 : 0;
   // K-contiguous A (forward, data gradients, LM head): the phase-staggered loop is 3-12 % faster; the K-strided
   // weight-gradient layout pays two transposed LDS reads per fragment in the load phases and stays on the 2-stage loop.
   return a.layout == PGCA_TN ? 0 : 6;
 }
+
+}  // namespace
 
 namespace pgca {
 GemmTuning& gemm_tuning() {
@@ -397,6 +309,44 @@ GemmTuning& gemm_tuning() {
     return v;
   }();
   return t;
+}
+
+// Kernel choice: big, K-aligned problems take the 256^2 LDS-DMA kernels, everything else the general 128^2
+// one.  Gradient-accumulating GEMMs with few output tiles but a long K (weight gradients: K = tokens) are split
+// along K so the 256^2 kernel still fills the chip; partials meet through f32 atomics.
+GemmPlan plan_gemm(const pgca_gemm_args& a) {
+  GemmPlan p;
+  p.ncols = a.epilogue == PGCA_EPI_DLOGITS ? a.out_cols : a.N;
+  const int ntm2 = (a.M + BM2 - 1) / BM2, ntn2 = (p.ncols + BN2 - 1) / BN2;
+  const int force = gemm_tuning().tile;
+  const int nk_total = a.K / BK;
+  int splits = 1;
+  const bool splittable = a.epilogue == PGCA_EPI_NONE && a.accumulate && a.out_f32 && !a.out_bf16 && !a.bias &&
+                          !a.residual;
+  if (splittable && ntm2 * ntn2 > 0 && ntm2 * ntn2 < 192) {  // no output tiles: nothing to divide by (check_gemm_args rejects the shape)
+    splits = 256 / (ntm2 * ntn2);
+    if (splits > nk_total / 8) splits = nk_total / 8;
+    if (splits > 16) splits = 16;
+    if (splits < 1) splits = 1;
+  }
+  const bool want256 = force ? force == 256 : (ntm2 * ntn2 * splits >= 192);
+  if ((a.K % BK) == 0 && want256 && a.M >= 8 && p.ncols >= 8) {
+    p.tile = 256;
+    p.variant = plan_variant(a);
+    p.splits = splits;
+    p.ntm = ntm2;
+    p.ntn = ntn2;
+    p.nk_per_split = (nk_total + splits - 1) / splits;
+    p.grid_y = (nk_total + p.nk_per_split - 1) / p.nk_per_split;
+  } else {
+    p.tile = 128;
+    p.variant = 0;
+    p.splits = p.grid_y = 1;
+    p.ntm = (a.M + BM - 1) / BM;
+    p.ntn = (p.ncols + BN - 1) / BN;
+    p.nk_per_split = (a.K + BK - 1) / BK;
+  }
+  return p;
 }
 }  // namespace pgca
 
@@ -420,10 +370,9 @@ extern "C" int pgca_set_option(const char* name, int32_t value) {
 }
 
 extern "C" int pgca_gemm_plan(const pgca_gemm_args* args) {
-  int splits = 1;
-  const int tile = plan_tile(*args, &splits);
-  if (tile != 256) return 12801;
-  return plan_variant(*args) * 1000000 + 25600 + splits;
+  const GemmPlan p = plan_gemm(*args);
+  if (p.tile != 256) return 12801;
+  return p.variant * 1000000 + 25600 + p.splits;
 }
 
 // Argument checks of pgca_gemm_bf16, shared with the paired launch.
@@ -483,39 +432,24 @@ static int check_gemm_args(const pgca_gemm_args& a) {
 extern "C" int pgca_gemm_bf16(const pgca_gemm_args* args, void* stream) {
   const pgca_gemm_args& a = *args;
   if (const int rc = check_gemm_args(a)) return rc;
-  const int ncols = a.epilogue == PGCA_EPI_DLOGITS ? a.out_cols : a.N;
+  const GemmPlan p = plan_gemm(a);
   hipStream_t s = (hipStream_t)stream;
-  {
-    const int ntm2 = (a.M + BM2 - 1) / BM2, ntn2 = (ncols + BN2 - 1) / BN2;
-    const int nk_total = a.K / BK;
-    int splits = 1;
-    const bool want256 = plan_tile(a, &splits) == 256;
-    if (want256) {
-      if (ensure_gemm256_attr()) return PGCA_ERR_LAUNCH;
-      pgca_gemm_args b = a;
-      if (splits > 1) b.accumulate = 2;
-      const int nkps = (nk_total + splits - 1) / splits;
-      dim3 grid2(ntm2 * ntn2, (nk_total + nkps - 1) / nkps), block2(512);
-      const int variant = plan_variant(a);
-      if (variant == 6) return launch_gemm256s(b, ntm2, ntn2, nkps, (int)grid2.y, stream);
-      switch (a.layout) {
-        case PGCA_NT: hipLaunchKernelGGL((gemm256_kernel<0, 0>), grid2, block2, GEMM256_LDS, s, b, ntm2, ntn2, nkps); break;
-        case PGCA_NN: hipLaunchKernelGGL((gemm256_kernel<0, 1>), grid2, block2, GEMM256_LDS, s, b, ntm2, ntn2, nkps); break;
-        case PGCA_TN: hipLaunchKernelGGL((gemm256_kernel<1, 1>), grid2, block2, GEMM256_LDS, s, b, ntm2, ntn2, nkps); break;
-        default: set_error("pgca_gemm_bf16: unknown layout %d", a.layout); return PGCA_ERR_INVALID;
-      }
-      return check_launch("pgca_gemm_bf16(256)");
-    }
-  }
-  const int ntm = (a.M + BM - 1) / BM, ntn = (ncols + BN - 1) / BN;
-  dim3 grid(ntm * ntn), block(256);
-  switch (a.layout) {
-    case PGCA_NT: hipLaunchKernelGGL((gemm_kernel<0, 0>), grid, block, 0, s, a, ntm, ntn); break;
-    case PGCA_NN: hipLaunchKernelGGL((gemm_kernel<0, 1>), grid, block, 0, s, a, ntm, ntn); break;
-    case PGCA_TN: hipLaunchKernelGGL((gemm_kernel<1, 1>), grid, block, 0, s, a, ntm, ntn); break;
-    default: set_error("pgca_gemm_bf16: unknown layout %d", a.layout); return PGCA_ERR_INVALID;
-  }
-  return check_launch("pgca_gemm_bf16");
+  if (p.tile == 128)
+    return with_layout(a.layout, [&](auto la, auto lb) {
+      hipLaunchKernelGGL((gemm_kernel<decltype(la)::value, decltype(lb)::value>), dim3(p.ntm * p.ntn), dim3(256), 0, s,
+                         a, p.ntm, p.ntn);
+      return check_launch("pgca_gemm_bf16");
+    });
+  pgca_gemm_args b = a;
+  if (p.splits > 1) b.accumulate = 2;
+  if (p.variant == 6) return launch_gemm256s(b, p, stream);
+  return with_layout(a.layout, [&](auto la, auto lb) {
+    constexpr auto kernel = gemm256_kernel<decltype(la)::value, decltype(lb)::value>;
+    if (raise_lds_limit<kernel>(GEMM256_LDS, "gemm256")) return (int)PGCA_ERR_LAUNCH;
+    hipLaunchKernelGGL(kernel, dim3(p.ntm * p.ntn, p.grid_y), dim3(512), GEMM256_LDS, s, b, p.ntm, p.ntn,
+                       p.nk_per_split);
+    return check_launch("pgca_gemm_bf16(256)");
+  });
 }
 
 extern "C" int pgca_gemm_bf16_grouped(const pgca_gemm_args* args, int32_t count, void* stream) {
@@ -526,26 +460,25 @@ extern "C" int pgca_gemm_bf16_grouped(const pgca_gemm_args* args, int32_t count,
   // Two NT or two NN problems of one shape that would each run the phase-staggered 256^2 kernel unsplit: one grid.
   if (count == 2 && gemm_tuning().group) {
     const pgca_gemm_args &a = args[0], &b = args[1];
-    int sa = 1, sb = 1;
-    const bool pair = (a.layout == PGCA_NT || a.layout == PGCA_NN) && b.layout == a.layout && a.M == b.M &&
-                      a.N == b.N && a.K == b.K && a.epilogue != PGCA_EPI_DLOGITS && b.epilogue != PGCA_EPI_DLOGITS &&
-                      plan_tile(a, &sa) == 256 && plan_tile(b, &sb) == 256 && sa == 1 && sb == 1 &&
-                      plan_variant(a) == 6 && plan_variant(b) == 6;
-    if (pair) {
+    const bool alike = (a.layout == PGCA_NT || a.layout == PGCA_NN) && b.layout == a.layout && a.M == b.M &&
+                       a.N == b.N && a.K == b.K && a.epilogue != PGCA_EPI_DLOGITS && b.epilogue != PGCA_EPI_DLOGITS;
+    const GemmPlan pa = alike ? plan_gemm(a) : GemmPlan{}, pb = alike ? plan_gemm(b) : GemmPlan{};
+    if (alike && pa.tile == 256 && pb.tile == 256 && pa.splits == 1 && pb.splits == 1 && pa.variant == 6 &&
+        pb.variant == 6) {
       for (int i = 0; i < 2; ++i) {
         const int rc = check_gemm_args(args[i]);
         if (rc) return rc;
       }
-      return launch_gemm256s_pair(a, b, stream);
+      return launch_gemm256s_pair(a, b, pa, stream);
     }
   }
   bool groupable = count <= 4 && gemm_tuning().group;
   for (int i = 0; i < count && groupable; ++i) {
     const pgca_gemm_args& a = args[i];
-    groupable = a.layout == PGCA_TN && a.A && a.B && a.K > 0 && (a.K % BK) == 0 && a.M >= 8 && a.N >= 8 &&
-                a.epilogue == PGCA_EPI_NONE && a.out_f32 && !a.out_bf16 && !a.bias && !a.residual &&
-                !a.drop_threshold && !(a.lda & 7) && !(a.ldb & 7) && !((uintptr_t)a.A & 15) && !((uintptr_t)a.B & 15) &&
-                a.lda >= ((a.M + 7) & ~7) && a.ldb >= ((a.N + 7) & ~7);
+    // what the grouped kernel needs beyond valid arguments: whole 64-deep K tiles, the plain accumulate-or-store epilogue
+    groupable = a.layout == PGCA_TN && (a.K % BK) == 0 && a.M >= 8 && a.N >= 8 && a.epilogue == PGCA_EPI_NONE &&
+                a.out_f32 && !a.out_bf16 && !a.bias && !a.residual && !a.drop_threshold &&
+                check_gemm_args(a) == PGCA_OK;
   }
   if (!groupable) {  // anything else: the ordinary path, one launch per problem
     for (int i = 0; i < count; ++i) {
@@ -554,7 +487,7 @@ extern "C" int pgca_gemm_bf16_grouped(const pgca_gemm_args* args, int32_t count,
     }
     return PGCA_OK;
   }
-  if (ensure_gemm256_attr()) return PGCA_ERR_LAUNCH;
+  if (raise_lds_limit<gemm256_group_tn_kernel>(GEMM256_LDS, "gemm256")) return PGCA_ERR_LAUNCH;
   pgca_group_param gp;
   int total = 0;
   for (int i = 0; i < 4; ++i) {

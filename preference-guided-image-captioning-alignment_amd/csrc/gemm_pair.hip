@@ -27,9 +27,9 @@ __global__ __launch_bounds__(512, 2) void gemm256s_pair_kernel(const pgca_pair_p
     bid = b - (p ? nwg : 0);
   } else {
     // every GROUP_M group before the one that holds b is full, so the division finds the group for the short last one too
-    const int per_group = 8 * ntn;
+    const int per_group = GROUP_M * ntn;
     const int g = b / (2 * per_group);
-    const int size = min(8, ntm - g * 8) * ntn;
+    const int size = min(GROUP_M, ntm - g * GROUP_M) * ntn;
     const int rem = b - g * 2 * per_group;
     p = rem >= size;
     bid = g * per_group + rem - (p ? size : 0);
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(512, 2) void gemm256s_pair_kernel(const pgca_pair_p
   bid = __builtin_amdgcn_readfirstlane(bid);
   // p is wave-uniform.  The problem's arguments are copied from the kernel argument segment at a[p] (gp is the only
   // explicit argument: offset 0) by scalar loads, into the SGPRs where the single launch holds its by-value
-  // pgca_gemm_args: 98 SGPRs, 256 VGPRs, no scratch, like gemm256s_kernel.  (Selecting field by field between a[0] and
+  // pgca_gemm_args: 100 SGPRs, 256 VGPRs, no scratch, like gemm256s_kernel.  (Selecting field by field between a[0] and
   // a[1] keeps both candidates live across the main loop: 106 SGPRs and spills.)
   const char* kernarg = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
   const pgca_gemm_args a = *(const pgca_gemm_args*)(kernarg + offsetof(pgca_pair_param, a) +
@@ -51,39 +51,29 @@ __global__ __launch_bounds__(512, 2) void gemm256s_pair_kernel(const pgca_pair_p
   gemm256s_body<LA, LB>(a, ntm, ntn, gp.nk, gp.stagger, bid, smems);
 }
 
-template <int LA, int LB>
-int launch_pair(const pgca_gemm_args& a0, const pgca_gemm_args& a1, hipStream_t s) {
-  static const bool attr_ok = hipFuncSetAttribute((const void*)gemm256s_pair_kernel<LA, LB>,
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)GEMM256S_LDS) == hipSuccess;
-  if (!attr_ok) {
-    (void)hipGetLastError();
-    set_error("gemm256s pair: cannot raise dynamic LDS limit");
-    return PGCA_ERR_LAUNCH;
-  }
-  pgca_pair_param gp;
-  gp.a[0] = a0;
-  gp.a[1] = a1;
-  gp.ntm = (a0.M + 255) / 256;
-  gp.ntn = (a0.N + 255) / 256;
-  gp.nk = a0.K / 64;  // in BK = 64 units like nk_per_split: the whole K, no split
-  gp.stagger = 2 * gp.ntm * gp.ntn >= 3 * 256 ? gemm_tuning().stagger : 0;
-  gp.order = gemm_tuning().pair_order;
-  hipLaunchKernelGGL((gemm256s_pair_kernel<LA, LB>), dim3(2 * gp.ntm * gp.ntn), dim3(512), GEMM256S_LDS, s, gp);
-  return check_launch("pgca_gemm_bf16_grouped(256 phase-staggered pair)");
-}
-
 }  // namespace
 
-int pgca::launch_gemm256s_pair(const pgca_gemm_args& a0, const pgca_gemm_args& a1, void* stream) {
+int pgca::launch_gemm256s_pair(const pgca_gemm_args& a0, const pgca_gemm_args& a1, const GemmPlan& p, void* stream) {
   // the paired kernel carries the forward epilogues only; any other kind runs as the two single launches
   // pgca_gemm_bf16 makes of these problems (256^2 tile, whole K)
   auto forward_epilogue = [](int e) { return (e >= PGCA_EPI_NONE && e <= PGCA_EPI_TANH) || e == PGCA_EPI_GELU_NEW_D; };
   if (!forward_epilogue(a0.epilogue) || !forward_epilogue(a1.epilogue)) {
-    const int ntm = (a0.M + 255) / 256, ntn = (a0.N + 255) / 256;
-    const int rc = launch_gemm256s(a0, ntm, ntn, a0.K / 64, 1, stream);
-    return rc ? rc : launch_gemm256s(a1, ntm, ntn, a1.K / 64, 1, stream);
+    const int rc = launch_gemm256s(a0, p, stream);
+    return rc ? rc : launch_gemm256s(a1, p, stream);
   }
-  hipStream_t s = (hipStream_t)stream;
-  return a0.layout == PGCA_NT ? launch_pair<0, 0>(a0, a1, s) : launch_pair<0, 1>(a0, a1, s);
+  pgca_pair_param gp;
+  gp.a[0] = a0;
+  gp.a[1] = a1;
+  gp.ntm = p.ntm;
+  gp.ntn = p.ntn;
+  gp.nk = p.nk_per_split;  // in BK = 64 units: the whole K, no split
+  gp.stagger = 2 * p.ntm * p.ntn >= 3 * 256 ? gemm_tuning().stagger : 0;
+  gp.order = gemm_tuning().pair_order;
+  auto launch = [&](auto lb) {  // A is K-contiguous in both layouts the caller pairs (NT, NN)
+    constexpr auto kernel = gemm256s_pair_kernel<0, decltype(lb)::value>;
+    if (raise_lds_limit<kernel>(GEMM256S_LDS, "gemm256s pair")) return (int)PGCA_ERR_LAUNCH;
+    hipLaunchKernelGGL(kernel, dim3(2 * p.ntm * p.ntn), dim3(512), GEMM256S_LDS, (hipStream_t)stream, gp);
+    return check_launch("pgca_gemm_bf16_grouped(256 phase-staggered pair)");
+  };
+  return a0.layout == PGCA_NT ? launch(std::integral_constant<int, 0>{}) : launch(std::integral_constant<int, 1>{});
 }

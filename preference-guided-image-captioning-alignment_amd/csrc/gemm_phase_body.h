@@ -22,47 +22,8 @@ namespace {
 constexpr int PBK = 32, PSTAGES = 4;
 constexpr int PTILE_BYTES = 256 * PBK * 2;  // 16 KiB per operand per stage
 
-__device__ __forceinline__ int swz4p(int q) { return (0x78 >> (2 * q)) & 3; }  // {0,2,3,1}
-
 template <int KS>
-struct DmaP {
-  unsigned goff[2];
-  __device__ __forceinline__ void init(int lane, int wave, int ld, int origin, int extent) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int j = wave * 2 + i;  // 1-KiB piece of the 16-KiB tile image
-      if (KS == 0) {               // [256 rows][32 k]: piece = 16 rows x 64 B; chunk c of row r at c ^ swz4p((r>>2)&3)
-        const int r = 16 * j + (lane >> 2);
-        const int c = (lane & 3) ^ swz4p((lane >> 4) & 3);
-        const int rg = min(origin + r, extent - 1) - origin;
-        goff[i] = (unsigned)(rg * ld + c * 8) * 2u;
-      } else {                     // [32 k][256 cols]: piece = 2 k-rows x 512 B (same image as the BK = 64 kernel)
-        const int k = 2 * j + (lane >> 5);
-        const int c16 = lane & 31;
-        const int h = (k & 3) | (((k >> 3) & 1) << 2);
-        const int col = (((c16 >> 1) ^ h) << 4) + ((c16 & 1) << 3);
-        const int cg = min(origin + col, extent - 8) - origin;
-        goff[i] = (unsigned)(k * ld + cg) * 2u;
-      }
-    }
-  }
-  __device__ __forceinline__ void issue(const bf16_t* base, unsigned char* tile, int wave) const {
-    const unsigned long long b = (unsigned long long)base;
-    u32x4 rs;
-    rs[0] = (unsigned)b;
-    rs[1] = (unsigned)(b >> 32) & 0xffffu;
-    rs[2] = 0x7ffffff0u;
-    rs[3] = 0x00020000u;
-    const unsigned lds0 = (unsigned)(size_t)LDS_PTR(tile) + (unsigned)wave * 2048u;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-                   :
-                   : "s"(lds0 + i * 1024u), "v"(goff[i]), "s"(rs)
-                   : "memory");
-    }
-  }
-};
+using DmaP = Dma<KS, PBK>;  // 2 pieces per wave; [256 rows][32 k] / [32 k][256 cols] images (gemm_device.h)
 
 template <int KS>
 __device__ __forceinline__ bf16x8 read_frag_p(const unsigned char* lds, int wbase, int sub, int lane) {
@@ -81,13 +42,6 @@ __device__ __forceinline__ void wait_vm_p() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// -DPGCA_GEMM_TIMING: main-loop / epilogue clocks per workgroup; -DPGCA_GEMM_TIMING2 adds per-phase clocks
-// (tools/gemm_bench.py --timing reads them from the stat_max / stat_sum buffers).  Stamps cost a lgkmcnt(0) each.
-#ifdef PGCA_GEMM_TIMING2
-#define PSTAMP(v) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory")
-#else
-#define PSTAMP(v)
-#endif
 // Diagnostic fillers (-DPGCA_FILL_L=n / -DPGCA_FILL_M=n): n independent VALU instructions per L phase (after its copy
 // instructions, before the barrier) / per MFMA gap.  They calibrate how much epilogue work of a PREVIOUS tile the main
 // loop could carry for free (tools/gemm_fill_probe.sh); never defined in the product build.
@@ -110,15 +64,15 @@ __device__ __forceinline__ void valu_fill(float (&d)[8]) {
   } while (0)
 
 // One tile of one problem.  `bid` = the workgroup's place in the XCD-remapped order of the problem's ntm x ntn tiles
-// (the caller applies the remap: a single-problem launch over its own grid, the paired launch over both problems).
+// (the caller applies xcd_remap: a single-problem launch over its own grid, the paired launch over both problems).
 template <int LA, int LB>
 __device__ __forceinline__ void gemm256s_body(const pgca_gemm_args& a, int ntm, int ntn, int nk_per_split, int stagger,
                                               int bid, unsigned char* smems) {  // smems: [4 stages][A 16 KiB | B 16 KiB]
 #ifdef PGCA_GEMM_TIMING
-  unsigned long long ts0, tr0;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts0)::"memory");
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tr0)::"memory");   // constant 100 MHz
+  unsigned long long ts0, ts1, ts2, ts3, tr0, tr3;
 #endif
+  TSTAMP(ts0);
+  TSTAMP_REAL(tr0);
 
   // De-phasing: with 128 KiB of LDS one workgroup owns a CU, every CU starts its tile at the same time and all 256
   // epilogues hit HBM together (store bursts at the HBM rate while the matrix pipes idle, then the reverse).  The
@@ -130,13 +84,8 @@ __device__ __forceinline__ void gemm256s_body(const pgca_gemm_args& a, int ntm, 
     for (int i = 0; i < slot * stagger; ++i) __builtin_amdgcn_s_sleep(16);  // 16 x 64 clocks
   }
 
-  constexpr int GROUP_M = 8;
-  const int per_group = GROUP_M * ntn;
-  const int group = bid / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsize = min(GROUP_M, ntm - first_m);
-  const int in_group = bid - group * per_group;
-  const int tm = first_m + in_group % gsize, tn = in_group / gsize;
+  int tm, tn;
+  group_m_tile(bid, ntm, ntn, tm, tn);
   const int m0 = tm * BM2, n0 = tn * BN2;
 
   const int t = threadIdx.x;
@@ -184,10 +133,7 @@ __device__ __forceinline__ void gemm256s_body(const pgca_gemm_args& a, int ntm, 
   PGCA_PBAR();                 // second barrier: same distance (two) as in the steady state
   if (wm == 1) PGCA_PBAR();    // group 1 runs one barrier late from here on
 
-#ifdef PGCA_GEMM_TIMING
-  unsigned long long ts1, ts2, ts3;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts1)::"memory");
-#endif
+  TSTAMP(ts1);
 #ifdef PGCA_GEMM_TIMING2
   unsigned long long q0 = 0, q1 = 0, q2 = 0, q3 = 0, q4 = 0, q5 = 0, q6 = 0, q7 = 0, q8 = 0;
   unsigned long long aL0 = 0, aB1 = 0, aM0 = 0, aB2 = 0, aL1 = 0, aB3 = 0, aM1 = 0, aB4 = 0;
@@ -275,29 +221,21 @@ __device__ __forceinline__ void gemm256s_body(const pgca_gemm_args& a, int ntm, 
   if (wm == 0) PGCA_PBAR();  // re-join the groups
   __syncthreads();           // the epilogue stages through the same LDS
 
+  TSTAMP(ts2);
+  run_epilogue(a, acc[0], smems, m0 + wm * 128, n0 + wn * 64, lane, wave);
+  run_epilogue(a, acc[1], smems, m0 + wm * 128 + 64, n0 + wn * 64, lane, wave);
 #ifdef PGCA_GEMM_TIMING
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts2)::"memory");
-#endif
-  run_epilogue(a, acc[0], smems, m0 + wm * 128, n0, tn, wn, lane, wave);
-  run_epilogue(a, acc[1], smems, m0 + wm * 128 + 64, n0, tn, wn, lane, wave);
-#ifdef PGCA_GEMM_TIMING
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts3)::"memory");
+  dma_wait();  // the stores have left
+  TSTAMP(ts3);
   if (a.stat_max && a.epilogue != PGCA_EPI_ROWSTATS && lane == 0) {
     float* o = a.stat_max + ((size_t)blockIdx.x * 8 + wave) * 8;
     o[0] = (float)(ts1 - ts0); o[1] = (float)(ts2 - ts1); o[2] = (float)(ts3 - ts2); o[3] = (float)(nk / 2);
     o[4] = (float)(ts0 & 0xFFFFFFFull); o[5] = (float)(ts3 & 0xFFFFFFFull);  // wrap at 2^28 clocks
     // in-kernel shader clock (MI355X_MICROARCH.md, DVFS item 6): (ts3 - ts0) / (tr3 - tr0) x 100 MHz
-    unsigned long long tr3;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tr3)::"memory");
+    TSTAMP_REAL(tr3);
     o[6] = (float)(ts3 - ts0); o[7] = (float)(tr3 - tr0);
   }
 #endif
-}
-
-// Workgroup b runs on XCD b % 8: XCD x walks a contiguous run of the `total` places.
-__device__ __forceinline__ int xcd_remap(int b, int total) {
-  const int xcd = b & 7, q = total >> 3, r = total & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
 }
 
 constexpr size_t GEMM256S_LDS = (size_t)2 * PSTAGES * PTILE_BYTES;  // 128 KiB

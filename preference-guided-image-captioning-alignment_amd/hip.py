@@ -221,19 +221,32 @@ def _gemm_args(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, layout:
     return a
 
 
+def _probe_begin(first: GemmArgs):
+    """``gemm_probe``, if set and interested in the plan of ``first``, gets HIP events on the launch stream that bracket
+    the one launch between this call and ``_probe_end`` (bench.py roofline measurement).  Without a probe the pair
+    allocates nothing: decoding records its launches into HIP graphs, and a garbage collection that an allocation
+    triggers inside a capture aborts the process."""
+    probe = gemm_probe
+    if probe is None or not probe.want(first.layout, first.epilogue, load().pgca_gemm_plan(C.byref(first))):
+        return None
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return probe, e0, e1
+
+
+def _probe_end(bracket, flops: float) -> None:
+    if bracket is not None:
+        probe, e0, e1 = bracket
+        e1.record()
+        probe.add(e0, e1, flops)
+
+
 def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, layout: int, **kw) -> None:
     """One ``pgca_gemm_bf16`` launch; the keywords are those of ``_gemm_args`` (the fields of ``pgca_gemm_args``)."""
     a = _gemm_args(A, B, M, N, K, layout, **kw)
-    probe = gemm_probe
-    if probe is not None and probe.want(layout, a.epilogue, load().pgca_gemm_plan(C.byref(a))):
-        # HIP events on the launch stream bracket this one kernel (bench.py roofline measurement)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _check(load().pgca_gemm_bf16(C.byref(a), _stream()), "pgca_gemm_bf16")
-        e1.record()
-        probe.add(e0, e1, 2.0 * M * N * K)
-        return
+    bracket = _probe_begin(a)
     _check(load().pgca_gemm_bf16(C.byref(a), _stream()), "pgca_gemm_bf16")
+    _probe_end(bracket, 2.0 * M * N * K)
 
 
 def gemm_pair(g0, g1) -> None:
@@ -243,31 +256,23 @@ def gemm_pair(g0, g1) -> None:
     arr = (GemmArgs * 2)()
     for a, (args, kw) in zip(arr, (g0, g1)):
         _gemm_args(*args, **kw, into=a)
-    probe = gemm_probe
-    if probe is not None and probe.want(arr[0].layout, arr[0].epilogue, load().pgca_gemm_plan(C.byref(arr[0]))):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _check(load().pgca_gemm_bf16_grouped(arr, 2, _stream()), "pgca_gemm_bf16_grouped")
-        e1.record()
-        probe.add(e0, e1, sum(2.0 * a.M * a.N * a.K for a in arr))
-        return
+    bracket = _probe_begin(arr[0])
     _check(load().pgca_gemm_bf16_grouped(arr, 2, _stream()), "pgca_gemm_bf16_grouped")
+    _probe_end(bracket, sum(2.0 * a.M * a.N * a.K for a in arr))
+
+
+def _wgrad_group_args(problems):
+    arr = (GemmArgs * len(problems))()
+    for a, (X, dY, M, N, K, gout) in zip(arr, problems):
+        _gemm_args(X, dY, M, N, K, TN, out_f32=gout, accumulate=True, into=a)
+    return arr
 
 
 def gemm_wgrad_group(problems) -> None:
     """problems: up to four (X [K, M] bf16, dY [K, N] bf16, M, N, K, grad [M, N] f32) tuples -> grad += X^t dY for
     each, in ONE launch (no split-K atomics).  The four weight gradients of a GPT-2 block."""
-    n = len(problems)
-    arr = (GemmArgs * n)()
-    for a, (X, dY, M, N, K, gout) in zip(arr, problems):
-        a.A, a.B = X.data_ptr(), dY.data_ptr()
-        a.M, a.N, a.K = M, N, K
-        a.lda, a.ldb = M, N
-        a.layout, a.epilogue, a.alpha = TN, EPI_NONE, 1.0
-        a.out_f32, a.ld_out_f32 = gout.data_ptr(), N
-        a.ld_out_bf16 = a.ld_res = a.ld_aux = N
-        a.accumulate = 1
-    _check(load().pgca_gemm_bf16_grouped(arr, n, _stream()), "pgca_gemm_bf16_grouped")
+    _check(load().pgca_gemm_bf16_grouped(_wgrad_group_args(problems), len(problems), _stream()),
+           "pgca_gemm_bf16_grouped")
 
 
 def gemm_skinny(x, W, M, N, K, scratch, *, lda=None, ldw=None, bias=None, act=EPI_NONE, residual=None, ld_res=None,

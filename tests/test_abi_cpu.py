@@ -80,3 +80,39 @@ def test_host_side_argument_validation_needs_no_gpu(lib):
     assert lib.pgca_gemm_skinny_workspace(1, 3072, 1024) > 0 and lib.pgca_gemm_skinny_workspace(0, 8, 8) == 0
     assert lib.pgca_seq_pack_prepare(None, 1, 16, 64, None, None, None, None, None, None, None) == -1
     assert lib.pgca_sqnorm_blocks(1) == 1 and lib.pgca_sqnorm_blocks(16384 * 3 + 1) == 4
+
+
+@pytest.mark.parametrize("layout", [hip.TN, hip.NT, hip.NN], ids=["TN", "NT", "NN"])
+def test_grouped_launch_rejects_empty_shapes_before_planning(lib, layout):
+    """Two problems in the weight-gradient form (plain epilogue, accumulate into f32: the split-K candidates) with no
+    output tiles are an argument error, found before the planner divides by the tile count."""
+    X, G = torch.zeros(64, 64, dtype=torch.bfloat16), torch.zeros(64, 64)
+    for M, N in ((0, 0), (0, 64), (64, 0), (-256, 64)):
+        arr = (hip.GemmArgs * 2)()
+        for a in arr:
+            hip._gemm_args(X, X, M, N, 64, layout, lda=64, ldb=64, out_f32=G, ld_out_f32=64, accumulate=True, into=a)
+        assert lib.pgca_gemm_bf16_grouped(arr, 2, None) == -1, (M, N)
+        assert b"empty shape" in lib.pgca_last_error()
+
+
+def test_wgrad_group_args_are_the_hand_filled_struct():
+    """``gemm_wgrad_group`` fills its array through ``_gemm_args``: every field of every problem equals the struct it
+    used to fill by hand (TN, alpha 1, accumulate into the f32 gradient, every leading dimension N, the rest zero)."""
+    problems = []
+    for M, N, K in ((512, 256, 2048), (256, 768, 200), (264, 520, 64)):
+        problems.append((torch.zeros(K, M, dtype=torch.bfloat16), torch.zeros(K, N, dtype=torch.bfloat16), M, N, K,
+                         torch.zeros(M, N)))
+    arr = hip._wgrad_group_args(problems)
+    assert len(arr) == len(problems)
+    for got, (X, dY, M, N, K, gout) in zip(arr, problems):
+        a = hip.GemmArgs()
+        a.A, a.B = X.data_ptr(), dY.data_ptr()
+        a.M, a.N, a.K = M, N, K
+        a.lda, a.ldb = M, N
+        a.layout, a.epilogue, a.alpha = hip.TN, hip.EPI_NONE, 1.0
+        a.out_f32, a.ld_out_f32 = gout.data_ptr(), N
+        a.ld_out_bf16 = a.ld_res = a.ld_aux = N
+        a.accumulate = 1
+        for name, _ in hip.GemmArgs._fields_:
+            assert getattr(got, name) == getattr(a, name), name
+        assert bytes(got) == bytes(a)

@@ -767,3 +767,98 @@ def test_gelu_with_saved_derivative_and_multiply_backward(hip, tile, shape):
     old = torch.empty_like(dpre)                                                   # and against the two-sigmoid pair
     hip.gemm(go, w2, M, N, 64, hip.NT, epilogue=hip.EPI_DGELU_NEW, aux_in=pre.detach().bfloat16(), out_bf16=old)
     close(dpre.float(), old.float(), 3e-2, "MUL_AUX vs DGELU_NEW")
+
+
+# ------------------------------------------------------------------------- every store epilogue, both fetch/store paths
+EPI_STORE_FORMS = ["NONE", "GELU_NEW", "QUICK_GELU", "RELU", "TANH", "GELU_NEW_D", "DGELU_NEW", "DQUICK_GELU", "DRELU",
+                   "DTANH", "MUL_AUX"]
+EPI_TRANSCENDENTAL = {"GELU_NEW", "QUICK_GELU", "TANH", "GELU_NEW_D", "DGELU_NEW", "DQUICK_GELU"}
+EPI_READS_AUX = {"DGELU_NEW", "DQUICK_GELU", "DRELU", "DTANH", "MUL_AUX"}
+_epilogue_case_cache = {}
+
+
+def epilogue_case():
+    """Inputs and fp32 references of test_gemm_epilogue_general_path_matches_reference, computed once for all tiles:
+    ``ref[form][run] = (result before accumulation, side value for aux_out or None)``."""
+    if _epilogue_case_cache:
+        return _epilogue_case_cache
+    M, N, K = 200, 136, 64
+    c = _epilogue_case_cache
+    c["A"] = rnd(M, K, scale=0.25, seed=71).bfloat16()
+    c["B"] = rnd(N, K, seed=72).bfloat16()                                      # NT: stored [N, K]
+    c["bias"], c["res"], c["old"] = rnd(N, seed=73), rnd(M, N, seed=74), rnd(M, N, seed=75)
+    c["x"] = rnd(M, N, seed=76).bfloat16()                                      # the saved activation (aux_in)
+    c["rows"] = torch.randperm(M, generator=torch.Generator().manual_seed(77)).int().to(dev())
+    c["seed"] = 0xBADC0DE
+    mult = drop_mult(c["seed"], 0.25, (M, N))[c["rows"].long()]                 # row m is hashed as row rows[m]
+    acc = c["A"].float() @ c["B"].float().t()
+    x = c["x"].float()
+
+    def dgelu_new(t):
+        t = t.clone().requires_grad_()
+        R.gelu_new(t).sum().backward()
+        return t.grad
+
+    def dquick_gelu(t):
+        s = torch.sigmoid(1.702 * t)
+        return s + 1.702 * t * s * (1 - s)
+
+    forms = {
+        "NONE": lambda p: (p, None), "GELU_NEW": lambda p: (R.gelu_new(p), p), "QUICK_GELU": lambda p: (R.quick_gelu(p), p),
+        "RELU": lambda p: (torch.relu(p), None), "TANH": lambda p: (torch.tanh(p), torch.tanh(p)),
+        "GELU_NEW_D": lambda p: (R.gelu_new(p), dgelu_new(p)), "DGELU_NEW": lambda p: (p * dgelu_new(x), None),
+        "DQUICK_GELU": lambda p: (p * dquick_gelu(x), None), "DRELU": lambda p: (p * (x > 0), None),
+        "DTANH": lambda p: (p * (1 - x * x), None), "MUL_AUX": lambda p: (p * x, None),
+    }
+    c["ref"] = {}
+    for name, form in forms.items():
+        yb, sb = form(acc + c["bias"])
+        y, s = form(acc)
+        c["ref"][name] = {"bias+residual": (yb + c["res"], sb), "accumulate": (y, s), "dropout": (y * mult, s)}
+    return c
+
+
+def test_gemm_epilogue_general_path_matches_reference(hip, tile):
+    """Every store epilogue through the masked general path - no test ran dropout, ``drop_rows`` or DQUICK_GELU there.
+    M = 200, N = 136: one interior 64 x 64 block and edge blocks in both directions under every tile; leading dimensions
+    of N + 1 (f32) / N + 4 (bf16) keep every block off the vector fast path, and the padding must stay untouched.  The
+    second pass, with aligned leading dimensions, sends the interior block down the fast path: same reference."""
+    M, N, K = 200, 136, 64
+    c = epilogue_case()
+    PAD = -77.0
+
+    def padded(ld, dtype, src=None):
+        buf = torch.full((M, ld), PAD, dtype=dtype, device=dev())
+        if src is not None:
+            buf[:, :N] = src
+        return buf
+
+    for ldf, ldb in ((N + 1, N + 4), (N, N)):
+        for name in EPI_STORE_FORMS:
+            tol_f, tol_b = (1.0 / 100, 1.0 / 100) if name in EPI_TRANSCENDENTAL else (2e-4, 1.0 / 128)
+            for run in ("bias+residual", "accumulate", "dropout"):
+                want, side = c["ref"][name][run]
+                out_f = padded(ldf, torch.float32, c["old"] if run == "accumulate" else None)
+                out_b = padded(ldb, torch.bfloat16)
+                kw = dict(epilogue=getattr(hip, "EPI_" + name), out_f32=out_f, ld_out_f32=ldf, out_bf16=out_b,
+                          ld_out_bf16=ldb, ld_aux=ldb)
+                aux = None
+                if name in EPI_READS_AUX:
+                    kw["aux_in"] = padded(ldb, torch.bfloat16, c["x"])
+                elif side is not None:
+                    aux = kw["aux_out"] = padded(ldb, torch.bfloat16)
+                if run == "bias+residual":
+                    kw.update(bias=c["bias"], residual=padded(ldf, torch.float32, c["res"]), ld_res=ldf)
+                elif run == "accumulate":
+                    kw.update(accumulate=True)
+                else:
+                    kw.update(drop=hip.drop_args(c["seed"], 0.25), drop_rows=c["rows"])
+                hip.gemm(c["A"], c["B"], M, N, K, hip.NT, **kw)
+                what = f"{name} {run} ld {ldf}/{ldb}"
+                close(out_f[:, :N], want + c["old"] if run == "accumulate" else want, tol_f, what + " f32")
+                close(out_b[:, :N], want, tol_b, what + " bf16")
+                if aux is not None:
+                    close(aux[:, :N], side, 1.0 / 100 if name in ("TANH", "GELU_NEW_D") else 1.0 / 128, what + " aux_out")
+                for buf in (out_f, out_b, aux, kw.get("residual"), kw.get("aux_in")):
+                    if buf is not None:
+                        assert bool((buf[:, N:] == PAD).all()), what + ": padding columns written"
