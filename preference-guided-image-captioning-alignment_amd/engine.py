@@ -13,8 +13,10 @@ Reference call sites replaced are cited per method.
 """
 from __future__ import annotations
 
+import logging
 import math
 import os
+from contextlib import contextmanager
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
@@ -24,6 +26,8 @@ import torch
 from . import hip
 from .arch import GptArch, ModelArch, VitArch
 from .params import ParamStore, Segment, VOCAB_TILE
+
+logger = logging.getLogger(__name__)
 
 F32, BF16, I32, I64 = torch.float32, torch.bfloat16, torch.int32, torch.int64
 ATTN_BWD_MAX_S = 1024        # include/pgca_hip.h PGCA_ATTN_SPLIT_MAX_S
@@ -48,6 +52,17 @@ class Workspace:
         self.device = torch.device(device)
         self.bufs: Dict[str, torch.Tensor] = {}
         self._stamps: Dict[str, tuple] = {}
+        # allocation serial of each key: goes up whenever the key gets NEW storage (``get`` regrows, ``cached`` rebuilds).
+        # Whoever keeps raw pointers into the workspace (a captured graph) compares serials, which never repeat; a
+        # ``data_ptr`` can, once the allocator hands a freed block out again
+        self.serial: Dict[str, int] = {}
+        self._recorders: List[set] = []
+
+    def _touch(self, key: str, fresh: bool) -> None:
+        if fresh:
+            self.serial[key] = self.serial.get(key, 0) + 1
+        for r in self._recorders:
+            r.add(key)
 
     def get(self, key: str, shape, dtype, zero: bool = False) -> torch.Tensor:
         shape = tuple(int(s) for s in shape)
@@ -55,10 +70,12 @@ class Workspace:
         for s in shape:
             n *= s
         t = self.bufs.get(key)
-        if t is None or t.dtype != dtype or t.numel() < n:
+        fresh = t is None or t.dtype != dtype or t.numel() < n
+        if fresh:
             grow = t is not None and t.dtype == dtype
             t = torch.empty(max(int(n * self.GROW) if grow else n, 1), dtype=dtype, device=self.device)
             self.bufs[key] = t
+        self._touch(key, fresh)
         v = t[:n].view(shape)
         if zero:
             v.zero_()
@@ -66,10 +83,27 @@ class Workspace:
 
     def cached(self, key: str, stamp: tuple, make) -> torch.Tensor:
         """Derived tensor (an index vector) kept under ``key``: ``make()`` builds it again only when ``stamp`` changes."""
-        if key not in self.bufs or self._stamps.get(key) != stamp:
+        fresh = key not in self.bufs or self._stamps.get(key) != stamp
+        if fresh:
             self.bufs[key] = make()
             self._stamps[key] = stamp
+        self._touch(key, fresh)
         return self.bufs[key]
+
+    @contextmanager
+    def recording(self):
+        """``with ws.recording() as keys``: ``keys`` collects every key asked for (``get`` / ``cached``) inside the block."""
+        keys: set = set()
+        self._recorders.append(keys)
+        try:
+            yield keys
+        finally:
+            self._recorders.remove(keys)
+
+    def stamp(self, keys) -> tuple:
+        """The ``(key, serial)`` pairs of ``keys``: equal to an earlier stamp of the same keys exactly while every one of
+        them is still the allocation it was then."""
+        return tuple((k, self.serial.get(k, 0)) for k in sorted(keys))
 
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.bufs.values())
@@ -357,6 +391,7 @@ class DecodeState:
     smax: int
     t: int = 0                 # position of the last step
     lnf_done: bool = False     # the last step left ln_f(x) in ``gen.y`` (skinny path): the LM head's operand
+    keys: frozenset = frozenset()   # workspace keys the decode's launches point into (``decode_begin`` records them)
 
 
 def _drive(steps):
@@ -557,7 +592,9 @@ class GptTrunk:
             raise ValueError(f"{smax} positions exceed GPT-2's {a.n_pos} learned positions")
         kv_all = self._buf("gen.kv", (len(self.layers), R * smax, 3 * H), BF16)
         att = self._buf("gen.att", (R * smax, H), BF16)
-        cu = self.ws.cached(self.tag + ".gen.cu", (R, smax),
+        # one vector per (R, smax): two decodes of equal R * smax that alternate neither rebuild it every time nor free the
+        # one a captured step of the other still reads
+        cu = self.ws.cached(f"{self.tag}.gen.cu.{R}x{smax}", (R, smax),
                             lambda: (torch.arange(R + 1, dtype=I32, device=self.ws.device) * smax).contiguous())
         return DecodeState(kv=list(kv_all), kv_all=kv_all, att=att, cu=cu, R=R, smax=smax)
 
@@ -985,6 +1022,8 @@ class CaptionDecoderEngine:
         self.saved = None
         self._dec: Optional[DecodeState] = None   # the decode in flight (decode_begin)
         self._graphs: dict = {}                   # captured decode steps (decode_advance)
+        self.graph_captures = 0                   # steps captured into a graph / steps served by replaying one
+        self.graph_replays = 0
 
     def _buf(self, name, shape, dtype, zero=False):
         return self.ws.get(f"{self.tag}.{name}", shape, dtype, zero)
@@ -1157,10 +1196,13 @@ class CaptionDecoderEngine:
         """Start an incremental decode from the prefix embeddings ``pv`` [R, H] (position 0); returns the logits of the
         first token [R, V].  ``max_positions`` = 1 + the most tokens that will be fed back."""
         R = pv.shape[0]
-        self._dec = self.trunk.decode_cache(R, int(max_positions))
-        x = self._buf("gen.x", (R, self.arch.gpt.hidden), F32)
-        torch.add(pv, self.wpe.w[0], out=x)
-        return self._decode_logits(x)
+        with self.ws.recording() as keys:
+            self._dec = self.trunk.decode_cache(R, int(max_positions))
+            x = self._buf("gen.x", (R, self.arch.gpt.hidden), F32)
+            torch.add(pv, self.wpe.w[0], out=x)
+            out = self._decode_logits(x)
+        self._dec.keys = frozenset(keys)
+        return out
 
     # One position of the decode is ~180 small launches (24 layers x 7 kernels); issued one by one from Python that is
     # 3.4 ms per token whatever the batch (measured: 165 ms per 49-token caption at batch 1, cache or no cache).  Each
@@ -1175,6 +1217,11 @@ class CaptionDecoderEngine:
         x.add_(self.wpe.w[t])
         return self._decode_logits(x)
 
+    def _graph_stamp(self, keys) -> tuple:
+        """What a captured step depends on staying put: the allocation serial of every workspace buffer its launches
+        read or write (``keys``), and the addresses of the parameters, which live outside the workspace."""
+        return (self.ws.stamp(keys), self.seg.bf16.data_ptr(), self.wte.w.data_ptr(), self.wpe.w.data_ptr())
+
     def decode_advance(self, tokens: torch.Tensor) -> torch.Tensor:
         """Feed the tokens chosen for the current position ([R] int64); returns the next token's logits [R, V]."""
         st = self._dec
@@ -1182,27 +1229,34 @@ class CaptionDecoderEngine:
         t = st.t
         if not (self.use_graphs and tokens.is_cuda):
             return self._advance_eager(tokens, t)
-        tok_in = self._buf("gen.tok_in", (st.R,), I64)
+        with self.ws.recording() as keys:
+            tok_in = self._buf("gen.tok_in", (st.R,), I64)
         tok_in.copy_(tokens)
-        # graphs hold raw pointers: they are only valid while every buffer they touch is the allocation they captured
-        stamp = (st.kv[0].data_ptr(), st.kv[-1].data_ptr(), st.att.data_ptr(), tok_in.data_ptr(),
-                 self.seg.bf16.data_ptr())
+        # a graph holds raw pointers: it may be replayed only while EVERY buffer its launches touch is the allocation it
+        # was captured with.  Each graph carries the keys that ``decode_begin`` and its own eager sizing call asked for,
+        # and their stamp
         cache = self._graphs
-        if cache.get("stamp") != stamp:
-            cache.clear()
-            cache["stamp"] = stamp
         key = (st.R, st.smax, t)
         g = cache.get(key)
         if g is not None:
-            g[0].replay()
-            return g[1]
-        out = self._advance_eager(tok_in, t)             # this call's result (also sizes every buffer)
+            if g[2] == self._graph_stamp(g[3]):
+                g[0].replay()
+                self.graph_replays += 1
+                return g[1]
+            for k in [k for k, v in cache.items() if v[2] != self._graph_stamp(v[3])]:
+                del cache[k]                                 # whatever moved took every graph that pointed at it along
+        with self.ws.recording() as step_keys:
+            out = self._advance_eager(tok_in, t)             # this call's result (also sizes every buffer)
+        keys = frozenset(keys | st.keys | step_keys)
         try:
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):                # records the same launches; nothing executes
+            with torch.cuda.graph(graph):                    # records the same launches; nothing executes
                 out_g = self._advance_eager(tok_in, t)
-            cache[key] = (graph, out_g)
-        except Exception:  # noqa: BLE001 - capture is an optimisation; the eager HIP launches above are the product path
+            cache[key] = (graph, out_g, self._graph_stamp(keys), keys)
+            self.graph_captures += 1
+        except Exception as e:  # noqa: BLE001 - capture is an optimisation; the eager HIP launches above are the product path
+            logger.warning("decode graphs turned off, every step now launches eagerly: capturing step %d of a %d x %d "
+                           "decode raised %s: %s", t, st.R, st.smax, type(e).__name__, e)
             self.use_graphs = False
             torch.cuda.synchronize()
         return out

@@ -330,10 +330,11 @@ class CaptionDecoder:
         if selection == "device":
             ids_buf, n = self._decode_device(pv, L, pad, eos, float(temperature), bool(do_sample), top_k, float(top_p),
                                              float(repetition_penalty), generator, use_cache, ngram, bans)[:2]
-            return self._trim(ids_buf, n, pad)
+            return ids_buf[:, :n]
         # ---- greedy / sampling (HF _sample): preallocated ids, one EOS read-back every EOS_CHECK tokens
         ids_buf = torch.full((B, L), pad, dtype=I64, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
+        stop = self._stop_column(L, dev)
         n = 0
         logits = eng.decode_begin(pv, L) if use_cache else None
         while True:
@@ -350,11 +351,14 @@ class CaptionDecoder:
             ids_buf[:, n] = nxt
             n += 1
             done = done | (nxt == eos)
-            if n == L or ((n % self.EOS_CHECK == 0) and bool(done.all())):   # the only host read-back of the loop
-                break
+            self._note_stop(stop, done, n)
+            if n == L or n % self.EOS_CHECK == 0:
+                cols = int(stop)                                 # the only host read-back of the loop
+                if cols <= n:
+                    break
             if use_cache:
                 logits = eng.decode_advance(nxt)
-        return self._trim(ids_buf, n, pad)
+        return ids_buf[:, :cols]
 
     def _ban_schedule(self, L, eos, min_length=0, min_new_tokens=None, suppress_tokens=None):
         """step -> device int64 ids banned in every row at that step (or None): ``suppress_tokens`` always, and [EOS]
@@ -371,18 +375,24 @@ class CaptionDecoder:
         early = torch.tensor(sup + [int(eos)], dtype=I64, device=dev) if min_new > 0 else None
         return lambda step: early if step < min_new else always
 
+    # Where the returned ids end (HF ``_sample``, the oracle's ``generate_greedy``): after the step at which the last row
+    # hit [EOS], or at L.  The loops look at ``done`` on the host only every EOS_CHECK steps and so may run on; the columns
+    # they fill past that step are all [PAD].  The step itself is therefore kept on the device - a 0-dim tensor that
+    # starts at L and drops to the first ``n`` at which ``done.all()`` held - and read back in place of the flag.  (It
+    # cannot be told from the ids: with ``pad == eos``, GPT-2's convention, a trailing [EOS] looks like padding.)
     @staticmethod
-    def _trim(ids_buf, n, pad):
-        # columns generated after every sequence had finished are all [PAD]: trimming them equals stopping at once
-        alive = (ids_buf[:, :n] != pad).any(dim=0)
-        last_tok = int(alive.nonzero().max()) + 1 if bool(alive.any()) else 1
-        return ids_buf[:, :max(1, min(n, last_tok))]
+    def _stop_column(L, dev):
+        return torch.full((), L, dtype=I64, device=dev)
+
+    @staticmethod
+    def _note_stop(stop, done, n):
+        stop.copy_(torch.where(done.all(), stop.clamp(max=n), stop))
 
     def _decode_device(self, pv, L, pad, eos, temperature, do_sample, top_k, top_p, repetition_penalty, generator,
                        use_cache=True, ngram=0, bans=lambda step: None):
         """The greedy / sampling loop of ``generate`` with one ``hip.select_token`` launch per step in place of the
         torch processors and draw (one uniform per row and step from ``generator``).  Returns (ids_buf [R, L], columns
-        filled, logp [R] = sum of the model's own log-probability of every generated token, [EOS] included and [PAD]
+        to return (``_stop_column``), logp [R] = sum of the model's own log-probability of every generated token, [EOS] included and [PAD]
         excluded, lengths [R] = how many tokens that is)."""
         eng, dev = self.engine, self._o.device
         R = pv.shape[0]
@@ -392,6 +402,7 @@ class CaptionDecoder:
         step_lp = torch.empty(R, dtype=F32, device=dev)
         logp = torch.zeros(R, dtype=F32, device=dev)
         lengths = torch.zeros(R, dtype=I64, device=dev)
+        stop = self._stop_column(L, dev)
         n = 0
         logits = eng.decode_begin(pv, L) if use_cache else None
         while True:
@@ -405,11 +416,14 @@ class CaptionDecoder:
             lengths += ~done
             n += 1
             done = done | (nxt == eos)
-            if n == L or ((n % self.EOS_CHECK == 0) and bool(done.all())):
-                break
+            self._note_stop(stop, done, n)
+            if n == L or n % self.EOS_CHECK == 0:
+                cols = int(stop)
+                if cols <= n:
+                    break
             if use_cache:
                 logits = eng.decode_advance(nxt)
-        return ids_buf, n, logp, lengths
+        return ids_buf, cols, logp, lengths
 
     def _beam_search(self, pv, B, nb, L, pad, eos, temperature, do_sample, top_p, repetition_penalty, generator,
                      use_cache, top_k=0, device_select=False, ngram=0, bans=lambda step: None, length_penalty=1.0,
@@ -508,7 +522,10 @@ class CaptionDecoder:
                 tok = torch.gather(topk_ids, 1, nxt_idx).view(R)
                 flat_src = (beam_src + ar * nb).view(R)
             # HF reads this flag back every step; here every EOS_CHECK steps: once no batch item can improve, the
-            # finished pool is closed to new entries (the -1e9 terms above), so the extra steps change nothing
+            # finished pool is closed to new entries (the -1e9 terms above), so the extra steps change nothing.
+            # ``~hits.all()`` loses nothing by being read this seldom: with one EOS id at most nb of the 2 * nb candidates
+            # can be [EOS], so it holds only when ``cur + 1 >= L`` made every candidate a hit - the step that ends the
+            # loop below anyway
             if cur >= L:
                 break
             if cur % self.EOS_CHECK == 0:
@@ -666,8 +683,7 @@ class PreferenceGuidedCaptioningModel:
                                                               max(0, int(top_k)), float(top_p), float(repetition_penalty),
                                                               generator, use_cache, max(0, int(no_repeat_ngram_size)),
                                                               bans)
-            ids = dec._trim(ids_buf, cols, base)
-            return ids.reshape(B, n, -1).contiguous(), logp.view(B, n), lengths.view(B, n)
+            return ids_buf[:, :cols].reshape(B, n, -1).contiguous(), logp.view(B, n), lengths.view(B, n)
         finally:
             self.train(was)
 

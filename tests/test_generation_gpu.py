@@ -77,6 +77,61 @@ def test_generation_loop_rules_reproduce_the_reference_generate(model, golden, m
     assert torch.equal(got, torch.from_numpy(g["beam4_eos_ids"]))
 
 
+_NEVER = None
+# step (column) at which each of three rows emits [EOS]; "pad_last": row 0 never does and emits the PAD id in the last column
+STOP_CASES = {
+    "eos_at_2_5_3": ((2, 5, 3), False),              # width 6: between two read-backs of the loop
+    "all_done_at_step_8": ((7, 3, 7), False),        # width 8: exactly at a read-back (EOS_CHECK)
+    "all_done_at_step_11": ((10, 4, 6), False),      # width 11: the loop runs on to 16
+    "one_row_never_finishes": ((2, _NEVER, 5), False),   # width L
+    "live_row_emits_pad_last": ((_NEVER, 3, 4), True),   # width L, the token kept
+}
+
+
+@pytest.mark.parametrize("selection", ["torch", "device"])
+@pytest.mark.parametrize("pad_is_eos", [True, False], ids=["pad_eq_eos", "pad_ne_eos"])
+@pytest.mark.parametrize("case", list(STOP_CASES))
+def test_greedy_stops_at_the_column_the_reference_stops_at(model, monkeypatch, case, pad_is_eos, selection):
+    """Scripted logits (every row's argmax at every step is chosen here), L = 20: the ids must be what HF's ``_sample``
+    and the oracle's ``generate_greedy`` return - every row's tokens up to and including its [EOS], the pad id after
+    it, and as many columns as the step at which the LAST row hit [EOS] (L when one never does) - whichever ids are
+    used for padding.  With ``pad == eos`` (GPT-2's convention) a trailing [EOS] cannot be told from padding, and a live
+    row may emit the pad id itself: the width must come from the loop's own bookkeeping, not from the ids."""
+    eng, arch = model.caption_decoder.engine, model.arch
+    L, V = 20, eng.V
+    eos = arch.gpt.base_vocab + 2
+    pad = eos if pad_is_eos else arch.gpt.base_vocab
+    eos_at, pad_last = STOP_CASES[case]
+    gen = torch.Generator().manual_seed(5)
+    script = torch.randint(0, arch.gpt.base_vocab, (3, L), generator=gen)     # ordinary tokens: neither pad nor eos
+    for r, e in enumerate(eos_at):
+        if e is not None:
+            script[r, e] = eos
+    if pad_last:
+        script[0, L - 1] = pad
+    # the rule of oracle/restatement.py generate_greedy (HF _sample), on the script
+    want, done = [], torch.zeros(3, dtype=torch.bool)
+    for n in range(L):
+        nxt = torch.where(done, torch.full((3,), pad), script[:, n])
+        want.append(nxt)
+        done = done | (nxt == eos)
+        if bool(done.all()):
+            break
+    want = torch.stack(want, dim=1)
+    assert want.shape[1] == max(e + 1 if e is not None else L for e in eos_at)   # max over rows of EOS index + 1, or L
+
+    def scripted(pv, ids):
+        out = torch.zeros(ids.shape[0], V, device=DEV)
+        out[torch.arange(ids.shape[0]), script[:, ids.shape[1]].to(DEV)] = 10.0
+        return out
+    monkeypatch.setattr(eng, "next_token_logits", scripted)
+    img = torch.randn(3, 3, arch.vit.image, arch.vit.image, generator=gen)
+    got = model.generate_token_ids(img, max_length=L + 1, num_beams=1, do_sample=False, repetition_penalty=1.0,
+                                   pad_token_id=pad, eos_token_id=eos, use_cache=False, selection=selection).cpu()
+    assert got.shape == want.shape, (tuple(got.shape), tuple(want.shape))
+    assert torch.equal(got, want)
+
+
 def test_cached_and_cache_free_generation_return_the_same_captions(model):
     """Free-running greedy and beam search, K/V cache against prefix recomputation, on a model whose logits are sharp
     enough for the comparison to mean something (tied embedding x 12)."""
