@@ -6,6 +6,12 @@
 
 using namespace pgca;
 
+// the problem both directions share, from an entry point's loose arguments (S is the padded length Sp as well)
+static AttnProblem problem(const void* qkv, const int32_t* key_mask, int B, int S, int heads, int causal, Drop drop,
+                           const int32_t* cu, void* stream) {
+  return {(const bf16_t*)qkv, key_mask, B, S, heads, causal, drop, cu, S, (hipStream_t)stream};
+}
+
 extern "C" int pgca_attention_fwd(const void* qkv, const int32_t* key_mask, int32_t B, int32_t S, int32_t heads,
                                   int32_t causal, void* out, float* lse, uint32_t drop_seed, uint32_t drop_threshold,
                                   float drop_scale, const int32_t* cu_seqlens, void* stream) {
@@ -13,8 +19,9 @@ extern "C" int pgca_attention_fwd(const void* qkv, const int32_t* key_mask, int3
     set_error("pgca_attention_fwd: bad arguments (B=%d S=%d heads=%d)", B, S, heads);
     return PGCA_ERR_INVALID;
   }
-  return attention_fwd_tiled(qkv, key_mask, B, S, heads, causal, out, lse, drop_seed, drop_threshold, drop_scale,
-                             cu_seqlens, stream);
+  const Drop drop{drop_seed, drop_threshold, drop_scale};
+  return attention_fwd_tiled({problem(qkv, key_mask, B, S, heads, causal, drop, cu_seqlens, stream), (bf16_t*)out,
+                              lse});
 }
 
 extern "C" int pgca_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
@@ -25,9 +32,9 @@ extern "C" int pgca_attention_bwd(const void* qkv, const void* out, const void* 
     set_error("pgca_attention_bwd: bad arguments (B=%d S=%d heads=%d; S must be <= %d)", B, S, heads, PGCA_ATTN_MAX_S);
     return PGCA_ERR_INVALID;
   }
-  return attention_bwd_tiled({(const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, key_mask, B, S, heads,
-                              causal, (bf16_t*)dqkv, Drop{drop_seed, drop_threshold, drop_scale}, cu_seqlens, S,
-                              (hipStream_t)stream});
+  const Drop drop{drop_seed, drop_threshold, drop_scale};
+  return attention_bwd_tiled({problem(qkv, key_mask, B, S, heads, causal, drop, cu_seqlens, stream),
+                              (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv});
 }
 
 // The same contract on the two-role kernels (a dK/dV role per 128-key block, a dQ role per 128-query block): one block's
@@ -42,7 +49,7 @@ extern "C" int pgca_attention_bwd_split(const void* qkv, const void* out, const 
               PGCA_ATTN_SPLIT_MAX_S);
     return PGCA_ERR_INVALID;
   }
-  return attention_bwd_split({(const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, key_mask, B, S, heads,
-                              causal, (bf16_t*)dqkv, Drop{drop_seed, drop_threshold, drop_scale}, cu_seqlens, S,
-                              (hipStream_t)stream});
+  const Drop drop{drop_seed, drop_threshold, drop_scale};
+  return attention_bwd_split({problem(qkv, key_mask, B, S, heads, causal, drop, cu_seqlens, stream),
+                              (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv});
 }

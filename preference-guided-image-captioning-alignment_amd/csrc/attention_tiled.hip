@@ -9,7 +9,8 @@
 // the k-slot <-> key map is the bijection {32s+4g+j, 32s+16+4g+j} and the V^t fragment is read with the same
 // map by ds_read_b64_tr_b16), so the probabilities never touch LDS.  O^t rows live on the same lanes as the softmax
 // statistics, so the running rescale is a per-lane scalar.  O leaves through a wave-private LDS transpose as 16-byte
-// row-contiguous stores.
+// row-contiguous stores.  One-tile sequences (S <= 128) take a four-wave kernel built from the same pieces: the two
+// forward kernels agree bit for bit wherever both can run.
 //
 // Backward: one workgroup per (head, batch) sweeps (key block, query block) pairs.  S and dP are computed with the KEY
 // on the lane, so P and dS accumulators feed dV^t += dO^t P and dK^t += Q^t dS directly as B operands; only dS crosses
@@ -32,11 +33,12 @@ constexpr int PS = 272;        // byte stride of a [.][128] bf16 row (256 + 16 p
 constexpr int TILE_QKV = TB * QS;  // 18432
 constexpr int TILE_P = TB * PS;    // 34816
 
-// rows row0 .. row0+127 of a [S][64] head slice (row stride ld elements) -> LDS image, zero rows >= S
+// rows row0 .. row0+127 of a [S][64] head slice (row stride ld elements) -> LDS image, zero rows >= S; NT threads
+template <int NT = TNT>
 __device__ __forceinline__ void stage_rows(unsigned char* lds, const bf16_t* g, int ld, int row0, int S, int t) {
 #pragma unroll
-  for (int i = 0; i < 1024 / TNT; ++i) {
-    const int idx = t + TNT * i;
+  for (int i = 0; i < 1024 / NT; ++i) {
+    const int idx = t + NT * i;
     const int row = idx >> 3, c = idx & 7;
     u32x4 v = (u32x4){0u, 0u, 0u, 0u};
     if (row0 + row < S) v = *reinterpret_cast<const u32x4*>(g + (size_t)(row0 + row) * ld + c * 8);
@@ -45,22 +47,25 @@ __device__ __forceinline__ void stage_rows(unsigned char* lds, const bf16_t* g, 
 }
 
 // the same in two halves, so that the global loads of several tiles can be in flight together before any of them is waited for
+template <int NT>
 struct StageRegs {
-  u32x4 v[1024 / TNT];
+  u32x4 v[1024 / NT];
 };
-__device__ __forceinline__ void stage_load(StageRegs& r, const bf16_t* g, int ld, int row0, int S, int t) {
+template <int NT>
+__device__ __forceinline__ void stage_load(StageRegs<NT>& r, const bf16_t* g, int ld, int row0, int S, int t) {
 #pragma unroll
-  for (int i = 0; i < 1024 / TNT; ++i) {
-    const int idx = t + TNT * i;
+  for (int i = 0; i < 1024 / NT; ++i) {
+    const int idx = t + NT * i;
     const int row = idx >> 3, c = idx & 7;
     r.v[i] = (u32x4){0u, 0u, 0u, 0u};
     if (row0 + row < S) r.v[i] = *reinterpret_cast<const u32x4*>(g + (size_t)(row0 + row) * ld + c * 8);
   }
 }
-__device__ __forceinline__ void stage_store(const StageRegs& r, unsigned char* lds, int t) {
+template <int NT>
+__device__ __forceinline__ void stage_store(const StageRegs<NT>& r, unsigned char* lds, int t) {
 #pragma unroll
-  for (int i = 0; i < 1024 / TNT; ++i) {
-    const int idx = t + TNT * i;
+  for (int i = 0; i < 1024 / NT; ++i) {
+    const int idx = t + NT * i;
     *reinterpret_cast<u32x4*>(lds + (idx >> 3) * QS + (idx & 7) * 16) = r.v[i];
   }
 }
@@ -105,140 +110,208 @@ __device__ __forceinline__ void store_rows16(const unsigned char* stage, int str
   }
 }
 
-// ------------------------------------------------------------------------------------ forward
-__global__ __launch_bounds__(TNT, 4) void attn_fwd_tiled_kernel(const bf16_t* __restrict__ qkv,
-                                                                const int* __restrict__ kmask, int S, int heads,
-                                                                int causal, bf16_t* __restrict__ out,
-                                                                float* __restrict__ lse_o, Drop drop,
-                                                                const int* __restrict__ cu, int Sp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* Ks = smem;
-  unsigned char* Vs = smem + TILE_QKV;
-  unsigned char* kms = smem + 2 * TILE_QKV;  // [128] bytes
+// ------------------------------------------------------------------------------------ both directions
+// What a workgroup of either direction knows about its (head, sequence): the clamped length, the head's base in qkv and
+// the thread indices.  row0 is the sequence's first token row (packed rows: see AttnProblem).
+struct HeadSeq {
+  const bf16_t* base;
+  int row0, S, H, ld, b, t, lane, w, g, i16;
+  unsigned bh;
+};
+__device__ __forceinline__ HeadSeq head_seq(const AttnProblem& a) {
+  HeadSeq c;
+  const int h = blockIdx.x;
+  c.b = blockIdx.y;
+  c.row0 = a.cu ? a.cu[c.b] : c.b * a.Sp;
+  c.S = a.cu ? min(a.S, a.cu[c.b + 1] - c.row0) : a.S;
+  c.H = a.heads * DH;
+  c.ld = 3 * c.H;
+  c.t = threadIdx.x;
+  c.lane = c.t & 63;
+  c.w = __builtin_amdgcn_readfirstlane(c.t >> 6);
+  c.g = c.lane >> 4;
+  c.i16 = c.lane & 15;
+  c.base = a.qkv + (size_t)c.row0 * c.ld + h * DH;
+  c.bh = (unsigned)c.b * a.heads + h;
+  return c;
+}
 
-  // Sp: the PADDED sequence length (geometry of key_mask, lse and the dropout index).  Packed rows (cu != NULL): this
-  // sequence's tokens are rows cu[b] .. cu[b+1]-1 and S is their count; otherwise rows b*Sp .. and S == Sp.
-  const int h = blockIdx.x, b = blockIdx.y, qb = blockIdx.z;
-  const int row0 = cu ? cu[b] : b * Sp;
-  if (cu) S = min(S, cu[b + 1] - row0);   // (a KV-cache launch gives cu the cache stride and S the filled length)
-  if (qb * TB >= S) return;  // block-uniform: a short (or empty) sequence has no such query block
-  const int H = heads * DH, ld = 3 * H;
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int g = lane >> 4, i16 = lane & 15;
-  const bf16_t* base = qkv + (size_t)row0 * ld + h * DH;
+// validity of the 128 keys from k0 (folds key < S)
+__device__ __forceinline__ void fill_kms(const AttnProblem& a, const HeadSeq& c, unsigned char* kms, int k0) {
+  if (c.t < TB) kms[c.t] = (k0 + c.t < c.S && (!a.kmask || a.kmask[c.b * a.Sp + k0 + c.t] != 0)) ? 1 : 0;
+}
 
-  const int qw = qb * TB + 16 * w;  // this wave's first query
-  const int q = qw + i16;
-  const bool wave_on = qw < S;      // wave-uniform
+// ------------------------------------------------------------------------------------ forward: the shared pieces
+// A forward workgroup's LDS is K | V | kms; one (16-query block, key tile) step is score_step -> prob_step -> pv_step, and
+// a block leaves through finish_block -> store_block.  Both kernels below are loops around these five, so every element
+// sees the same products in the same order whichever kernel computes it: with an incoming maximum of -inf the key-tiled
+// kernel's first rescale multiplies exact zeros, and the two agree bit for bit wherever both can run.
+struct FwdBlock : HeadSeq {
+  unsigned char *Ks, *Vs;  // [128][64] bf16 images of the current key tile
+  unsigned char* kms;      // [128]
+  bf16_t* obase;
+  float* lse_row;          // NULL when the caller keeps no lse
+};
+__device__ __forceinline__ FwdBlock fwd_block(unsigned char* smem, const AttnFwd& a) {
+  FwdBlock c;
+  static_cast<HeadSeq&>(c) = head_seq(a);
+  c.Ks = smem;
+  c.Vs = smem + TILE_QKV;
+  c.kms = smem + 2 * TILE_QKV;
+  c.obase = a.out + (size_t)c.row0 * c.H + blockIdx.x * DH;
+  c.lse_row = a.lse ? a.lse + (size_t)c.bh * a.Sp : nullptr;
+  return c;
+}
 
-  bf16x8 fq[2];
+// lane (g, i16)'s share of the Q rows of a 16-query block as the B operand of S^t = K Q^t (n = query q), zero for q >= S
+__device__ __forceinline__ void q_frags(const FwdBlock& c, int q, bf16x8 (&fq)[2]) {
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
     u32x4 v = (u32x4){0u, 0u, 0u, 0u};
-    if (q < S) v = *reinterpret_cast<const u32x4*>(base + (size_t)q * ld + kk * 32 + g * 8);
+    if (q < c.S) v = *reinterpret_cast<const u32x4*>(c.base + (size_t)q * c.ld + kk * 32 + c.g * 8);
     fq[kk] = __builtin_bit_cast(bf16x8, v);
   }
+}
+
+// Scores of query q against the first ntile 16-key tiles of the staged key tile (keys k0 ..): scaled, -inf where the key
+// is invalid (kms already folds key < S), past the diagonal or in a tile the block does not need.  The keys of a query
+// live on (mi, g, r).  Returns the query's maximum folded with mx.
+__device__ __forceinline__ float score_step(const AttnProblem& a, const FwdBlock& c, const bf16x8 (&fq)[2], int k0, int q,
+                                            int ntile, float mx, f32x4 (&acc)[8]) {
+  const float scale = 0.125f;
+#pragma unroll
+  for (int mi = 0; mi < 8; ++mi) {
+    acc[mi] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (mi < ntile) {
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+        acc[mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(c.Ks, mi * 16, kk, c.lane), fq[kk], acc[mi], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int mi = 0; mi < 8; ++mi) {
+    // the 4 validity bytes of this lane's keys of tile mi in one LDS word
+    const unsigned kv = *reinterpret_cast<const unsigned*>(c.kms + mi * 16 + c.g * 4);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = k0 + mi * 16 + c.g * 4 + r;
+      const bool ok = mi < ntile && ((kv >> (8 * r)) & 1u) && (!a.causal || key <= q);
+      const float s = ok ? acc[mi][r] * scale : -INFINITY;
+      acc[mi][r] = s;
+      mx = fmaxf(mx, s);
+    }
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 16));
+  return fmaxf(mx, __shfl_xor(mx, 32));
+}
+
+// Scores -> dropped probabilities exp(s - mx) * m, in place; returns this lane's share of the UNDROPPED row sum.
+// Attention-probability dropout (GPT-2 attn_dropout, modeling_gpt2.py:66) acts on the NORMALISED probability: the mask
+// multiplies the numerator only.
+__device__ __forceinline__ float prob_step(const AttnProblem& a, const FwdBlock& c, int k0, int q, int ntile, float mx,
+                                           f32x4 (&acc)[8]) {
+  const unsigned dbase = (c.bh * a.Sp + q) * a.Sp;
+  float psum = 0.f;
+#pragma unroll
+  for (int mi = 0; mi < 8; ++mi) {
+    float dm[4] = {1.f, 1.f, 1.f, 1.f};
+    if (a.drop.on() && mi < ntile) a.drop.mul4(dbase + (unsigned)(k0 + mi * 16 + c.g * 4), dm);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float p = acc[mi][r] > -INFINITY ? __expf(acc[mi][r] - mx) : 0.f;
+      psum += p;
+      acc[mi][r] = p * dm[r];
+    }
+  }
+  return psum;
+}
+
+// O^t[d][q] += V^t[d][key] P^t[key][q], 32 keys per step: two stacked probability tiles are the B operand as they stand
+__device__ __forceinline__ void pv_step(const FwdBlock& c, int ntile, const f32x4 (&acc)[8], f32x4 (&oT)[4]) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    if (2 * s < ntile) {
+      const float lo[4] = {acc[2 * s][0], acc[2 * s][1], acc[2 * s][2], acc[2 * s][3]};
+      const float hi[4] = {acc[2 * s + 1][0], acc[2 * s + 1][1], acc[2 * s + 1][2], acc[2 * s + 1][3]};
+      const bf16x8 fp = pack_acc(lo, hi);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+        oT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(c.Vs, QS, s * 32, dt * 16, c.lane), fp, oT[dt], 0, 0, 0);
+    }
+  }
+}
+
+// The end of query q's row: the four g-lanes' partial sums make l, lse = m + log l goes out, O^t / l is packed to bf16
+__device__ __forceinline__ void finish_block(const FwdBlock& c, int q, float m, float l, const f32x4 (&oT)[4],
+                                             u32x2 (&opk)[4]) {
+  l += __shfl_xor(l, 16);
+  l += __shfl_xor(l, 32);
+  const float inv = l > 0.f ? 1.f / l : 0.f;
+  if (c.lane < 16 && q < c.S && c.lse_row) c.lse_row[q] = m + __logf(l);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) {
+    opk[dt][0] = pack2(oT[dt][0] * inv, oT[dt][1] * inv);
+    opk[dt][1] = pack2(oT[dt][2] * inv, oT[dt][3] * inv);
+  }
+}
+
+// The packed block of the queries qw .. qw+15 (block-local rows lrow ..) leaves through K's LDS rows lrow .. lrow+15, which
+// only this wave touches once every wave is done with K
+__device__ __forceinline__ void store_block(const FwdBlock& c, int lrow, int qw, const u32x2 (&opk)[4]) {
+  unsigned char* stage = c.Ks + lrow * QS;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<u32x2*>(stage + c.i16 * QS + (dt * 16 + c.g * 4) * 2) = opk[dt];
+  store_rows16(stage, QS, c.obase, c.H, qw, min(16, c.S - qw), c.lane);
+}
+
+// ------------------------------------------------------------------------------------ forward, any S
+// One 8-wave workgroup per (head, sequence, 128-query block): wave w owns 16 queries and sweeps the key tiles with an
+// online softmax - the rescale by alpha is all this kernel adds to the shared pieces.
+__global__ __launch_bounds__(TNT, 4) void attn_fwd_tiled_kernel(const AttnFwd a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const FwdBlock c = fwd_block(smem, a);
+  const int S = c.S, w = c.w, qb = blockIdx.z;
+  if (qb * TB >= S) return;  // block-uniform: a short (or empty) sequence has no such query block
+  const int qw = qb * TB + 16 * w;  // this wave's first query
+  const int q = qw + c.i16;
+  const bool wave_on = qw < S;      // wave-uniform
+  bf16x8 fq[2];
+  q_frags(c, q, fq);
 
   float m_run = -INFINITY, l_run = 0.f;
   f32x4 oT[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) oT[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const float scale = 0.125f;
-  const int nkt = causal ? qb + 1 : (S + TB - 1) / TB;
-  const unsigned dbase = (((unsigned)b * heads + h) * Sp + q) * Sp;
+  const int nkt = a.causal ? qb + 1 : (S + TB - 1) / TB;
 
   for (int kt = 0; kt < nkt; ++kt) {
     const int k0 = kt * TB;
     __syncthreads();  // every wave is done with the previous key tile
-    stage_rows(Ks, base + H, ld, k0, S, t);
-    stage_rows(Vs, base + 2 * H, ld, k0, S, t);
-    if (t < TB) kms[t] = (k0 + t < S && (!kmask || kmask[b * Sp + k0 + t] != 0)) ? 1 : 0;
+    stage_rows(c.Ks, c.base + c.H, c.ld, k0, S, c.t);
+    stage_rows(c.Vs, c.base + 2 * c.H, c.ld, k0, S, c.t);
+    fill_kms(a, c, c.kms, k0);
     __syncthreads();
     if (!wave_on) continue;
 
     const int nvalid = min(8, (S - k0 + 15) >> 4);
-    const int ntile = (causal && kt == qb) ? min(w + 1, nvalid) : nvalid;  // 16-key tiles this wave needs
-
+    const int ntile = (a.causal && kt == qb) ? min(w + 1, nvalid) : nvalid;  // 16-key tiles this wave needs
     f32x4 acc[8];
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) {
-      acc[mi] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (mi < ntile) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-          acc[mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(Ks, mi * 16, kk, lane), fq[kk], acc[mi], 0, 0, 0);
-      }
-    }
-    // scale + mask; running maximum of this query (keys live on (mi, g, r))
-    float mx = m_run;
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) {
-      // the 4 validity bytes of this lane's keys of tile mi in one LDS word (kms already folds key < S)
-      const unsigned kv = *reinterpret_cast<const unsigned*>(kms + mi * 16 + g * 4);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = k0 + mi * 16 + g * 4 + r;
-        const bool ok = mi < ntile && ((kv >> (8 * r)) & 1u) && (!causal || key <= q);
-        const float s = ok ? acc[mi][r] * scale : -INFINITY;
-        acc[mi][r] = s;
-        mx = fmaxf(mx, s);
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float mx = score_step(a, c, fq, k0, q, ntile, m_run, acc);
     const float alpha = mx > -INFINITY ? __expf(m_run - mx) : 1.f;  // exp(-inf) = 0 when this is the first live tile
     m_run = mx;
-    float psum = 0.f;
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) {
-      // attention-probability dropout (GPT-2 attn_dropout, modeling_gpt2.py:66) acts on the NORMALISED probability:
-      // the mask multiplies the numerator only, the row sum stays undropped
-      float dm[4] = {1.f, 1.f, 1.f, 1.f};
-      if (drop.on() && mi < ntile) drop.mul4(dbase + (unsigned)(k0 + mi * 16 + g * 4), dm);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = acc[mi][r] > -INFINITY ? __expf(acc[mi][r] - mx) : 0.f;
-        psum += p;
-        acc[mi][r] = p * dm[r];
-      }
-    }
+    const float psum = prob_step(a, c, k0, q, ntile, mx, acc);
     l_run = l_run * alpha + psum;  // per-lane partial; the four g-lanes of a query are summed once at the end
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) oT[dt][r] *= alpha;
-    // O^t[d][q] += V^t[d][key] P^t[key][q], 32 keys per step
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if (2 * s < ntile) {
-        const float lo[4] = {acc[2 * s][0], acc[2 * s][1], acc[2 * s][2], acc[2 * s][3]};
-        const float hi[4] = {acc[2 * s + 1][0], acc[2 * s + 1][1], acc[2 * s + 1][2], acc[2 * s + 1][3]};
-        const bf16x8 fp = pack_acc(lo, hi);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-          oT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(Vs, QS, s * 32, dt * 16, lane), fp, oT[dt], 0, 0, 0);
-      }
-    }
+    pv_step(c, ntile, acc, oT);
   }
 
-  float l = l_run;
-  l += __shfl_xor(l, 16);
-  l += __shfl_xor(l, 32);
-  const float inv = l > 0.f ? 1.f / l : 0.f;
-  if (lane < 16 && q < S && lse_o) lse_o[((size_t)b * heads + h) * Sp + q] = m_run + __logf(l);
-
+  u32x2 opk[4];
+  finish_block(c, q, m_run, l_run, oT, opk);
   __syncthreads();  // Ks is free: it becomes the output staging (wave w uses rows 16w..16w+15 only)
-  unsigned char* stage = Ks + (16 * w) * QS;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    u32x2 pk;
-    pk[0] = pack2(oT[dt][0] * inv, oT[dt][1] * inv);
-    pk[1] = pack2(oT[dt][2] * inv, oT[dt][3] * inv);
-    *reinterpret_cast<u32x2*>(stage + i16 * QS + (dt * 16 + g * 4) * 2) = pk;
-  }
-  if (wave_on) store_rows16(stage, QS, out + (size_t)row0 * H + h * DH, H, qw, min(16, S - qw), lane);
+  if (wave_on) store_block(c, 16 * w, qw, opk);
 }
 
 // ------------------------------------------------------------------------------------ forward, S <= 128
@@ -249,55 +322,33 @@ __global__ __launch_bounds__(TNT, 4) void attn_fwd_tiled_kernel(const bf16_t* __
 // idle when the sequence is short (packed captions average 72 tokens: 5 of 8 waves had queries, and a sequence of <= 64
 // tokens now occupies 4 wave slots instead of 8), (iii) needs no online-softmax rescale: one key tile, one maximum.
 constexpr int FNT = 256;
-__global__ __launch_bounds__(FNT, 4) void attn_fwd_one_kernel(const bf16_t* __restrict__ qkv,
-                                                              const int* __restrict__ kmask, int S, int heads, int causal,
-                                                              bf16_t* __restrict__ out, float* __restrict__ lse_o,
-                                                              Drop drop, const int* __restrict__ cu, int Sp) {
+__global__ __launch_bounds__(FNT, 4) void attn_fwd_one_kernel(const AttnFwd a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* Ks = smem;
-  unsigned char* Vs = smem + TILE_QKV;
-  unsigned char* kms = smem + 2 * TILE_QKV;  // [128] bytes
-  const int h = blockIdx.x, b = blockIdx.y;
-  const int row0 = cu ? cu[b] : b * Sp;
-  if (cu) S = min(S, cu[b + 1] - row0);
+  const FwdBlock c = fwd_block(smem, a);
+  const int S = c.S, w = c.w;
   if (S <= 0) return;
-  const int H = heads * DH, ld = 3 * H;
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int g = lane >> 4, i16 = lane & 15;
-  const bf16_t* base = qkv + (size_t)row0 * ld + h * DH;
 
-  // all of this workgroup's loads are requested before anything waits: K, V (4 + 4 chunks per thread) and both Q blocks
-  u32x4 rk[4], rv[4];
+  // all of this workgroup's loads are requested before anything waits: K, V (4 + 4 chunks per thread) and both Q blocks.
+  // (K and V share one bounds test here instead of two stage_load calls: behind those the compiler waits for six of the
+  // twelve requests instead of three, 1 % of the kernel on packed captions.)
+  StageRegs<FNT> rk, rv;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int idx = t + FNT * i, row = idx >> 3, c = idx & 7;
-    rk[i] = rv[i] = (u32x4){0u, 0u, 0u, 0u};
+  for (int i = 0; i < 1024 / FNT; ++i) {
+    const int idx = c.t + FNT * i, row = idx >> 3, ch = idx & 7;
+    rk.v[i] = rv.v[i] = (u32x4){0u, 0u, 0u, 0u};
     if (row < S) {
-      rk[i] = *reinterpret_cast<const u32x4*>(base + H + (size_t)row * ld + c * 8);
-      rv[i] = *reinterpret_cast<const u32x4*>(base + 2 * H + (size_t)row * ld + c * 8);
+      rk.v[i] = *reinterpret_cast<const u32x4*>(c.base + c.H + (size_t)row * c.ld + ch * 8);
+      rv.v[i] = *reinterpret_cast<const u32x4*>(c.base + 2 * c.H + (size_t)row * c.ld + ch * 8);
     }
   }
   bf16x8 fq[2][2];
 #pragma unroll
-  for (int ps = 0; ps < 2; ++ps)
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int q = 64 * ps + 16 * w + i16;
-      u32x4 v = (u32x4){0u, 0u, 0u, 0u};
-      if (q < S) v = *reinterpret_cast<const u32x4*>(base + (size_t)q * ld + kk * 32 + g * 8);
-      fq[ps][kk] = __builtin_bit_cast(bf16x8, v);
-    }
-  if (t < TB) kms[t] = (t < S && (!kmask || kmask[b * Sp + t] != 0)) ? 1 : 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int idx = t + FNT * i, row = idx >> 3, c = idx & 7;
-    *reinterpret_cast<u32x4*>(Ks + row * QS + c * 16) = rk[i];
-    *reinterpret_cast<u32x4*>(Vs + row * QS + c * 16) = rv[i];
-  }
+  for (int ps = 0; ps < 2; ++ps) q_frags(c, 64 * ps + 16 * w + c.i16, fq[ps]);
+  fill_kms(a, c, c.kms, 0);
+  stage_store(rk, c.Ks, c.t);
+  stage_store(rv, c.Vs, c.t);
   __syncthreads();
 
-  const float scale = 0.125f;
   const int nvalid = min(8, (S + 15) >> 4);
   u32x2 opk[2][4];  // the two blocks' outputs, packed bf16, until K's space can stage them
 #pragma unroll
@@ -306,106 +357,45 @@ __global__ __launch_bounds__(FNT, 4) void attn_fwd_one_kernel(const bf16_t* __re
     for (int dt = 0; dt < 4; ++dt) opk[ps][dt] = (u32x2){0u, 0u};
     const int qw = 64 * ps + 16 * w;  // this wave's first query of the block
     if (qw < S) {                      // wave-uniform
-      const int q = qw + i16;
-      const int ntile = causal ? min((qw >> 4) + 1, nvalid) : nvalid;  // 16-key tiles this block needs
-      f32x4 acc[8];
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi) {
-        acc[mi] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (mi < ntile) {
-#pragma unroll
-          for (int kk = 0; kk < 2; ++kk)
-            acc[mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rows64(Ks, mi * 16, kk, lane), fq[ps][kk], acc[mi], 0, 0,
-                                                              0);
-        }
-      }
-      float mx = -INFINITY;
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi) {
-        const unsigned kv = *reinterpret_cast<const unsigned*>(kms + mi * 16 + g * 4);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int key = mi * 16 + g * 4 + r;
-          const bool ok = mi < ntile && ((kv >> (8 * r)) & 1u) && (!causal || key <= q);
-          const float sc = ok ? acc[mi][r] * scale : -INFINITY;
-          acc[mi][r] = sc;
-          mx = fmaxf(mx, sc);
-        }
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 16));
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const unsigned dbase = (((unsigned)b * heads + h) * Sp + q) * Sp;
-      float l = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi) {
-        float dm[4] = {1.f, 1.f, 1.f, 1.f};
-        if (drop.on() && mi < ntile) drop.mul4(dbase + (unsigned)(mi * 16 + g * 4), dm);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pr = acc[mi][r] > -INFINITY ? __expf(acc[mi][r] - mx) : 0.f;
-          l += pr;
-          acc[mi][r] = pr * dm[r];
-        }
-      }
-      f32x4 oT[4];
+      const int q = qw + c.i16;
+      const int ntile = a.causal ? min((qw >> 4) + 1, nvalid) : nvalid;  // 16-key tiles this block needs
+      f32x4 acc[8], oT[4];
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) oT[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) {
-        if (2 * s4 < ntile) {
-          const float lo[4] = {acc[2 * s4][0], acc[2 * s4][1], acc[2 * s4][2], acc[2 * s4][3]};
-          const float hi[4] = {acc[2 * s4 + 1][0], acc[2 * s4 + 1][1], acc[2 * s4 + 1][2], acc[2 * s4 + 1][3]};
-          const bf16x8 fp = pack_acc(lo, hi);
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt)
-            oT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_acc(Vs, QS, s4 * 32, dt * 16, lane), fp, oT[dt], 0, 0, 0);
-        }
-      }
-      l += __shfl_xor(l, 16);
-      l += __shfl_xor(l, 32);
-      const float inv = l > 0.f ? 1.f / l : 0.f;
-      if (lane < 16 && q < S && lse_o) lse_o[((size_t)b * heads + h) * Sp + q] = mx + __logf(l);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        opk[ps][dt][0] = pack2(oT[dt][0] * inv, oT[dt][1] * inv);
-        opk[ps][dt][1] = pack2(oT[dt][2] * inv, oT[dt][3] * inv);
-      }
+      const float mx = score_step(a, c, fq[ps], 0, q, ntile, -INFINITY, acc);
+      const float l = prob_step(a, c, 0, q, ntile, mx, acc);
+      pv_step(c, ntile, acc, oT);
+      finish_block(c, q, mx, l, oT, opk[ps]);
     }
   }
   __syncthreads();  // every wave is done with K: its rows become the output staging (block ps of wave w: rows 64ps + 16w ..)
 #pragma unroll
   for (int ps = 0; ps < 2; ++ps) {
     const int qw = 64 * ps + 16 * w;
-    if (qw < S) {
-      unsigned char* stage = Ks + qw * QS;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<u32x2*>(stage + i16 * QS + (dt * 16 + g * 4) * 2) = opk[ps][dt];
-      store_rows16(stage, QS, out + (size_t)row0 * H + h * DH, H, qw, min(16, S - qw), lane);
-    }
+    if (qw < S) store_block(c, qw, qw, opk[ps]);
   }
 }
 
 // ------------------------------------------------------------------------------------ backward: the shared pieces
 // What a backward workgroup knows about its (head, sequence): the LDS carve-up K | V | Q | dO | [dS^t] | lse | delta | kms,
-// the clamped length, the head's global bases and the thread indices.  ALIAS (one (key, query) pair at a time only): the
-// dS^t image lives where V and Q were - both are dead once phase A is over - so a workgroup needs 75 KiB of LDS instead
-// of 109 and two of them share a CU (registers capped at 128 for that).
-struct BwdBlock {
+// the head's other global bases and, from HeadSeq, the clamped length and the thread indices.  ALIAS (one (key, query) pair
+// at a time only): the dS^t image lives where V and Q were - both are dead once phase A is over - so a workgroup needs
+// 75 KiB of LDS instead of 109 and two of them share a CU (registers capped at 128 for that).
+struct BwdBlock : HeadSeq {
   unsigned char *Ks, *Vs, *Qs, *dOs;  // [128][64] bf16 images
   unsigned char* dSs;                 // dS^t image [128 keys][128 queries]
   unsigned char* mine;                // this wave's own 16 rows of the dS^t image (also its store staging)
   float *lses, *dels;                 // [NQB * 128] each
   unsigned char* kms;                 // [128]
-  const bf16_t *base, *obase, *dobase;
+  const bf16_t *obase, *dobase;
   bf16_t* dbase_g;
   const float* lse_row;
-  int S, H, ld, b, t, lane, w, g, i16;
-  unsigned bh;
 };
 template <int NQB, bool ALIAS>
 __device__ __forceinline__ BwdBlock bwd_block(unsigned char* smem, const AttnBwd& a) {
   static_assert(!ALIAS || (NQB == 1 && TILE_P <= 2 * TILE_QKV), "the dS^t image must fit where V and Q were");
   BwdBlock c;
+  static_cast<HeadSeq&>(c) = head_seq(a);
   c.Ks = smem;
   c.Vs = smem + TILE_QKV;
   c.Qs = smem + 2 * TILE_QKV;
@@ -415,29 +405,17 @@ __device__ __forceinline__ BwdBlock bwd_block(unsigned char* smem, const AttnBwd
   c.dels = c.lses + NQB * TB;
   c.kms = reinterpret_cast<unsigned char*>(c.dels + NQB * TB);
   const int h = blockIdx.x;
-  c.b = blockIdx.y;
-  const int row0 = a.cu ? a.cu[c.b] : c.b * a.Sp;  // packed rows: see the forward
-  c.S = a.cu ? min(a.S, a.cu[c.b + 1] - row0) : a.S;
-  c.H = a.heads * DH;
-  c.ld = 3 * c.H;
-  c.t = threadIdx.x;
-  c.lane = c.t & 63;
-  c.w = __builtin_amdgcn_readfirstlane(c.t >> 6);
-  c.g = c.lane >> 4;
-  c.i16 = c.lane & 15;
   c.mine = c.dSs + (16 * c.w) * PS;
-  c.base = a.qkv + (size_t)row0 * c.ld + h * DH;
-  c.obase = a.O + (size_t)row0 * c.H + h * DH;
-  c.dobase = a.dO + (size_t)row0 * c.H + h * DH;
-  c.dbase_g = a.dqkv + (size_t)row0 * c.ld + h * DH;
-  c.lse_row = a.lse + ((size_t)c.b * a.heads + h) * a.Sp;
-  c.bh = (unsigned)c.b * a.heads + h;
+  c.obase = a.O + (size_t)c.row0 * c.H + h * DH;
+  c.dobase = a.dO + (size_t)c.row0 * c.H + h * DH;
+  c.dbase_g = a.dqkv + (size_t)c.row0 * c.ld + h * DH;
+  c.lse_row = a.lse + (size_t)c.bh * a.Sp;
   return c;
 }
 
 // rows of one 128-query block: delta[row] = sum_d dO[row, d] O[row, d] from the requested registers (8 lanes per row; the
 // (row, chunk) map is stage_load's)
-__device__ __forceinline__ void delta_rows(const StageRegs& po, const StageRegs& pdo, float* dels, int t) {
+__device__ __forceinline__ void delta_rows(const StageRegs<TNT>& po, const StageRegs<TNT>& pdo, float* dels, int t) {
 #pragma unroll
   for (int i = 0; i < 1024 / TNT; ++i) {
     const int idx = t + TNT * i;
@@ -460,7 +438,7 @@ __device__ __forceinline__ void delta_rows(const StageRegs& po, const StageRegs&
 // the first MFMA instead of three.  With packed sequences (mean length 72 of 128) most workgroups have exactly one pair.
 template <int NROWS>
 struct PairRegs {
-  StageRegs k, v, q, dO, o;
+  StageRegs<TNT> k, v, q, dO, o;
   float lse[(NROWS + TNT - 1) / TNT];
 };
 template <int NROWS>
@@ -495,11 +473,6 @@ __device__ __forceinline__ void store_first_pair(const BwdBlock& c, const PairRe
   stage_store(r.q, c.Qs, c.t);
   stage_store(r.dO, c.dOs, c.t);
   store_row_consts(c, c.t, r);
-}
-
-// validity of the 128 keys from k0 (folds key < S)
-__device__ __forceinline__ void fill_kms(const AttnBwd& a, const BwdBlock& c, int k0) {
-  if (c.t < TB) c.kms[c.t] = (k0 + c.t < c.S && (!a.kmask || a.kmask[c.b * a.Sp + k0 + c.t] != 0)) ? 1 : 0;
 }
 
 // this wave's 16 keys of the staged K and V as B operands (n = key)
@@ -673,7 +646,7 @@ __global__ __launch_bounds__(TNT, ALIAS ? 4 : 2) void attn_bwd_tiled_kernel(cons
       stage_rows(c.Ks, c.base + c.H, c.ld, k0, S, t);
       stage_rows(c.Vs, c.base + 2 * c.H, c.ld, k0, S, t);
     }
-    fill_kms(a, c, k0);
+    fill_kms(a, c, c.kms, k0);
     __syncthreads();
     const int keyw = k0 + 16 * w;            // this wave's first key
     const bool has_keys = keyw < S;          // wave-uniform
@@ -764,7 +737,7 @@ __device__ __forceinline__ void dkv_role(unsigned char* smem, const AttnBwd& a, 
   PairRegs<TB> r;
   load_first_pair(c, k0, qb0 * TB, r);
   store_first_pair(c, r);
-  fill_kms(a, c, k0);
+  fill_kms(a, c, c.kms, k0);
   const int keyw = k0 + 16 * w;            // this wave's first key
   const bool has_keys = keyw < S;          // wave-uniform
   const int key = keyw + c.i16;
@@ -841,7 +814,7 @@ __device__ __forceinline__ void dq_role(unsigned char* smem, const AttnBwd& a, i
       stage_rows(c.Vs, c.base + 2 * c.H, c.ld, k0, S, tl);
       stage_rows(c.Qs, c.base, c.ld, q0, S, tl);
     }
-    fill_kms(a, c, k0);
+    fill_kms(a, c, c.kms, k0);
     __syncthreads();
     const int keyw = k0 + 16 * w;            // this wave's first key
     int ll = c.lane;   // (so are the per-lane tile offsets)
@@ -924,24 +897,19 @@ int attention_bwd_split(const AttnBwd& a) {
   return check_launch("pgca_attention_bwd_split");
 }
 
-int attention_fwd_tiled(const void* qkv, const int32_t* key_mask, int B, int S, int heads, int causal, void* out,
-                        float* lse, uint32_t drop_seed, uint32_t drop_threshold, float drop_scale, const int32_t* cu,
-                        void* stream) {
+int attention_fwd_tiled(const AttnFwd& a) {
   static const hipError_t attr = hipFuncSetAttribute((const void*)attn_fwd_tiled_kernel,
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)TFWD_LDS);
   if (attr != hipSuccess) {
     set_error("attention (tiled forward): cannot raise dynamic LDS limit");
     return PGCA_ERR_LAUNCH;
   }
-  if (S <= TB) {  // one key tile: the four-wave kernel
-    hipLaunchKernelGGL(attn_fwd_one_kernel, dim3(heads, B), dim3(FNT), TFWD_LDS, (hipStream_t)stream, (const bf16_t*)qkv,
-                       key_mask, S, heads, causal, (bf16_t*)out, lse, Drop{drop_seed, drop_threshold, drop_scale}, cu, S);
+  if (a.S <= TB) {  // one key tile: the four-wave kernel
+    hipLaunchKernelGGL(attn_fwd_one_kernel, dim3(a.heads, a.B), dim3(FNT), TFWD_LDS, a.stream, a);
     return check_launch("pgca_attention_fwd(one tile)");
   }
-  const int nqb = (S + TB - 1) / TB;
-  hipLaunchKernelGGL(attn_fwd_tiled_kernel, dim3(heads, B, nqb), dim3(TNT), TFWD_LDS, (hipStream_t)stream,
-                     (const bf16_t*)qkv, key_mask, S, heads, causal, (bf16_t*)out, lse,
-                     Drop{drop_seed, drop_threshold, drop_scale}, cu, S);
+  const int nqb = (a.S + TB - 1) / TB;
+  hipLaunchKernelGGL(attn_fwd_tiled_kernel, dim3(a.heads, a.B, nqb), dim3(TNT), TFWD_LDS, a.stream, a);
   return check_launch("pgca_attention_fwd(tiled)");
 }
 

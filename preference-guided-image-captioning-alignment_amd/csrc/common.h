@@ -134,22 +134,30 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* addr0, const unsi
   return __builtin_bit_cast(bf16x8, r);
 }
 
-// attention_tiled.hip's launchers behind the C entry points of attention.hip, which check the arguments.  The
-// backward's travel as one struct, from the entry point into the kernels.
-struct AttnBwd {
-  const bf16_t *qkv, *O, *dO;
-  const float* lse;
+// attention_tiled.hip's launchers behind the C entry points of attention.hip, which check the arguments.  Each
+// direction's arguments travel as one struct, from the entry point into the kernels; the problem itself is their base.
+struct AttnProblem {
+  const bf16_t* qkv;
   const int32_t* kmask;
   int B, S, heads, causal;
-  bf16_t* dqkv;
   Drop drop;
+  // Sp: the PADDED sequence length (geometry of key_mask, lse and the dropout index).  Packed rows (cu != NULL): sequence
+  // b's tokens are rows cu[b] .. cu[b+1]-1 and S bounds their count; otherwise rows b*Sp .. and S == Sp.  (A KV-cache
+  // launch gives cu the cache stride and S the filled length.)
   const int32_t* cu;
-  int Sp;  // the padded sequence length (geometry of key_mask, lse and the dropout index): see the forward kernel
+  int Sp;
   hipStream_t stream;
 };
-int attention_fwd_tiled(const void* qkv, const int32_t* key_mask, int B, int S, int heads, int causal, void* out,
-                        float* lse, uint32_t drop_seed, uint32_t drop_threshold, float drop_scale, const int32_t* cu,
-                        void* stream);
+struct AttnFwd : AttnProblem {
+  bf16_t* out;
+  float* lse;  // may be NULL (the decode step keeps none)
+};
+struct AttnBwd : AttnProblem {
+  const bf16_t *O, *dO;
+  const float* lse;
+  bf16_t* dqkv;
+};
+int attention_fwd_tiled(const AttnFwd& a);
 int attention_bwd_tiled(const AttnBwd& a);  // one pass, S <= PGCA_ATTN_MAX_S
 int attention_bwd_split(const AttnBwd& a);  // split by role, S <= PGCA_ATTN_SPLIT_MAX_S
 

@@ -69,6 +69,37 @@ def test_tiled_attention_dropout_replay(hip, S):
     close(dqkv, x.grad, 1.0 / 40, "attn bwd with replayed dropout")
 
 
+@pytest.mark.parametrize("holes", [False, True])
+@pytest.mark.parametrize("causal", [True, False])
+def test_one_tile_and_key_tiled_forward_are_one_arithmetic(hip, causal, holes):
+    """The decode path crosses from the four-wave one-tile kernel (S <= 128) to the eight-wave key-tiled kernel inside
+    one generation, so the two must be the same arithmetic.  With packed rows the launch argument S only bounds the
+    per-sequence length: the same rows launched with S = 128 and S = 129 run one kernel each and must agree bit for bit
+    (block edges, the 64-row second block, one-row and full sequences).  No dropout: its counter depends on S."""
+    heads = 2
+    H = heads * 64
+    lens = [128, 127, 113, 100, 67, 65, 64, 63, 17, 16, 1]
+    B, rows = len(lens), sum(lens)
+    cu = torch.tensor([0] + lens).cumsum(0).int().to(dev())
+    qkv = rnd(rows, 3 * H, seed=31).bfloat16()
+    res = []
+    for S in (128, 129):
+        mask = None
+        if holes:   # keys 3 and 70 are invalid where the row has them (never key 0: no causal row is left empty)
+            mask = torch.ones(B, S, dtype=torch.int32)
+            mask[:, 3] = 0
+            mask[:, 70] = 0
+            mask = mask.to(dev())
+        out = torch.full((rows, H), 7.0, dtype=torch.bfloat16, device=dev())
+        lse = torch.zeros(B, heads, S, device=dev())
+        hip.attention_fwd(qkv, mask, B, S, heads, causal, out, lse, cu=cu)
+        res.append((out, lse))
+    (out1, lse1), (out2, lse2) = res
+    assert torch.equal(out1, out2)
+    for b, n in enumerate(lens):
+        assert torch.equal(lse1[b, :, :n], lse2[b, :, :n]), b
+
+
 def test_tiled_attention_is_reproducible(hip):
     """No atomics anywhere: two launches on the same inputs are bitwise equal."""
     B, S, heads = 4, 256, 4
