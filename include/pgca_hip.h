@@ -397,7 +397,9 @@ int pgca_masked_mean_fwd(const float* feats, const int32_t* mask, int32_t B, int
                          const int32_t* cu_seqlens, void* stream);
 int pgca_masked_mean_bwd(const float* dpooled, const int32_t* mask, int32_t B, int32_t S, int32_t H,
                          float* dfeats, const int32_t* cu_seqlens, void* stream);
-/* y = x / max(||x||, 1e-12) (F.normalize, model.py:828-829) and its backward. */
+/* y = x / max(||x||, 1e-12) (F.normalize, model.py:828-829) and its backward dx = (dy - y (dy . y)) / norm; a row whose
+ * norm was clamped (norm <= 1e-12) is divided by a constant, so its backward is dy / norm (autograd passes nothing through
+ * clamp_min there). */
 int pgca_l2norm_fwd(const float* x, int32_t B, int32_t P, float* y, float* norm, void* stream);
 int pgca_l2norm_bwd(const float* dy, const float* y, const float* norm, int32_t B, int32_t P, float* dx,
                     void* stream);

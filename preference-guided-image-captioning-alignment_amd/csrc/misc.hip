@@ -317,6 +317,9 @@ __global__ void l2norm_bwd_kernel(const float* __restrict__ dy, const float* __r
   float s = 0.f;
   for (int c = lane; c < P; c += 64) s += dy[(size_t)r * P + c] * y[(size_t)r * P + c];
   s = wave_sum(s);
+  // a row whose norm was clamped is divided by the CONSTANT 1e-12: nothing flows back through the norm
+  // (F.normalize is x / norm.clamp_min(eps), model.py:828-829), so the projection term drops out
+  if (!(norm[r] > 1e-12f)) s = 0.f;
   const float inv = 1.f / norm[r];
   for (int c = lane; c < P; c += 64) dx[(size_t)r * P + c] = (dy[(size_t)r * P + c] - y[(size_t)r * P + c] * s) * inv;
 }

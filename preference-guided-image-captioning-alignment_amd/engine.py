@@ -13,6 +13,7 @@ Reference call sites replaced are cited per method.
 """
 from __future__ import annotations
 
+import gc
 import logging
 import math
 import os
@@ -1248,6 +1249,12 @@ class CaptionDecoderEngine:
         with self.ws.recording() as step_keys:
             out = self._advance_eager(tok_in, t)             # this call's result (also sizes every buffer)
         keys = frozenset(keys | st.keys | step_keys)
+        # No garbage collection inside the capture: the ~180 launches allocate enough Python objects to trigger one, and a
+        # collection that frees a dead cycle holding device memory or another model's graphs (torch.cuda.graph no longer
+        # collects before it captures) releases them in the middle of the capture, which aborts the process.  The dead
+        # cycles are collected by the next automatic collection outside the capture.
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
         try:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):                    # records the same launches; nothing executes
@@ -1259,6 +1266,9 @@ class CaptionDecoderEngine:
                            "decode raised %s: %s", t, st.R, st.smax, type(e).__name__, e)
             self.use_graphs = False
             torch.cuda.synchronize()
+        finally:
+            if gc_was_enabled:
+                gc.enable()
         return out
 
     def decode_reorder(self, src: torch.Tensor) -> None:

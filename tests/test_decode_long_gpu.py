@@ -1,6 +1,7 @@
 """The K/V-cache decode where ``generate`` is allowed to go but no other test does: past one 128-key tile (the
 eight-wave online-softmax attention kernel on a strided cache), and across everything that can move a buffer under a
 captured decode step (regrown workspace buffers, alternating decode shapes, a capture that fails)."""
+import gc
 import logging
 from dataclasses import replace
 
@@ -161,5 +162,43 @@ def test_captured_steps_are_replayed_only_on_the_buffers_they_were_captured_with
         assert torch.equal(out, want_d)
         assert len(warned) == 1 and "no graphs today" in warned[0].getMessage(), [r.getMessage() for r in warned]
         assert eng.use_graphs is False
+    finally:
+        eng.use_graphs = True
+
+
+def test_no_garbage_collection_inside_a_decode_capture(tiny, monkeypatch):
+    """A collection inside a graph capture can free a dead cycle that holds device memory or another model's graphs in the
+    middle of the capture, which aborts the process; ``torch.cuda.graph`` does not collect before it captures.  So the
+    collector is off from before the capture begins until it has ended, and back on afterwards - also when the capture
+    fails."""
+    arch, eng = tiny.arch, tiny.caption_decoder.engine
+    seen = []
+    real = torch.cuda.graph
+
+    class Watched(real):
+        def __enter__(self):
+            seen.append(gc.isenabled())
+            return super().__enter__()
+
+        def __exit__(self, *exc):
+            seen.append(gc.isenabled())
+            return super().__exit__(*exc)
+    monkeypatch.setattr(torch.cuda, "graph", Watched)
+    emb, toks = _inputs(arch, 5, 4, 9)
+    pv = eng.prefix_embedding(emb)
+    assert gc.isenabled()
+    try:
+        c = eng.graph_captures
+        out = _decode(eng, pv, toks, 4, True)
+        assert eng.use_graphs and eng.graph_captures - c == 3
+        assert seen == [False] * 6 and gc.isenabled()
+        assert torch.equal(out, _decode(eng, pv, toks, 4, False))
+
+        def broken(*a, **k):
+            raise RuntimeError("no graphs today")
+        monkeypatch.setattr(torch.cuda, "CUDAGraph", broken)
+        emb, toks = _inputs(arch, 6, 3, 10)
+        _decode(eng, eng.prefix_embedding(emb), toks, 3, True)
+        assert eng.use_graphs is False and gc.isenabled()
     finally:
         eng.use_graphs = True
