@@ -321,7 +321,7 @@ int pgca_image_preprocess(const uint8_t* images, int32_t B, int32_t H, int32_t W
  * RandomResizedCrop(S, scale (0.8, 1), ratio (0.75, 1.33)) -> RandomHorizontalFlip -> ColorJitter(0.2, 0.2, 0.2, 0.1) ->
  * RandomRotation(5) -> ToTensor -> Normalize), BIT-EXACT with torchvision's PIL backend GIVEN the random draws, which
  * stay on the host (pgca_amd.input.draw_train_params restates torchvision's get_params).  Per image b:
- *   params int32 [B, 20]: crop box i, j, h, w (top, left, height, width; inside the H x W image) | flip 0/1 |
+ *   params int32 [B, PGCA_TRAIN_PARAM_INTS]: crop box i, j, h, w (top, left, height, width; inside the H x W image) | flip 0/1 |
  *     the four ColorJitter operations in their drawn order (0 brightness, 1 contrast, 2 saturation, 3 hue) |
  *     hue turn = uint8(hue_factor * 255) | rotate 0/1 (0: angle % 360 == 0, PIL copies) |
  *     a0 a1 a2 a3 a4 a5: Geometry.c affine_fixed's 16.16 integers of the output->input map | 3 unused;
@@ -331,6 +331,7 @@ int pgca_image_preprocess(const uint8_t* images, int32_t B, int32_t H, int32_t W
  * tmp u8 [B, H, S, 3] and resized_u8 u8 [B, S, S, 3] are scratch (the latter returns the cropped + resized image);
  * aug_u8 (optional) u8 [B, S, S, 3] receives the augmented image before ToTensor; out f32 [B, 3, S, S].
  * The jitter + rotation stage keeps one S x S x 3 image in LDS: S <= 230 (every shipped config uses 224). */
+#define PGCA_TRAIN_PARAM_INTS 20 /* int32 values per image in `params` */
 int pgca_image_train_transform(const uint8_t* images, int32_t B, int32_t H, int32_t W, int32_t S, const int32_t* params,
                                const float* factors, const int32_t* xbounds, const int32_t* xcoef, int32_t xk,
                                const int32_t* ybounds, const int32_t* ycoef, int32_t yk, float mean0, float mean1,

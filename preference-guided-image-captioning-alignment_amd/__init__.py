@@ -3,6 +3,7 @@
 Only what the Stage-1 NT-Xent step and the Stage-2 DPO step need lives here:
 
 * ``csrc/``      hand-written HIP kernels for gfx950 + the C-ABI (``include/pgca_hip.h``)
+* ``abi``        reader of ``include/pgca_hip.h``: prototypes, structs and constants the binding is derived from
 * ``hip``        ctypes binding of ``libpgca_hip.so`` (fails loudly when the library is missing)
 * ``arch``       tower geometries (ViT / GPT-2 families named by the reference configs)
 * ``params``     flat HBM parameter store with the reference's ``state_dict`` key names

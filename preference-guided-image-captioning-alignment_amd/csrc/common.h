@@ -22,6 +22,13 @@ namespace pgca {
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 
+// argument check of a C entry point: records the failed condition for pgca_last_error() and returns
+#define REQUIRE(cond, who)                        \
+  if (!(cond)) {                                  \
+    set_error(who ": bad arguments (" #cond ")"); \
+    return PGCA_ERR_INVALID;                      \
+  }
+
 __device__ __forceinline__ float bf2f(bf16_t v) { return (float)v; }
 __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)v; }
 

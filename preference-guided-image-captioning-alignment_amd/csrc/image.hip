@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void resample_v_norm_kernel(const unsigned cha
 //        Convert.c's HSV round trip) and the nearest-neighbour rotation gather (Geometry.c affine_fixed, 16.16 fixed
 //        point), then ToTensor + Normalize straight into the f32 planes.
 // Byte and integer work plus a little float arithmetic that must round as the C library's does: contraction is off.
-constexpr int TP_INTS = 20;  // per image: i, j, h, w, flip, order[4], hue shift, rotate?, a0..a5, pad[3]
+constexpr int TP_INTS = PGCA_TRAIN_PARAM_INTS;  // per image: i, j, h, w, flip, order[4], hue shift, rotate?, a0..a5, pad[3]
 
 __global__ __launch_bounds__(256) void crop_resample_h_kernel(const unsigned char* __restrict__ in, int H, int W, int S,
                                                               const int* __restrict__ params,

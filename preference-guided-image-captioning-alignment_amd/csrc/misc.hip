@@ -577,12 +577,6 @@ inline int blocks_for(long long work, int per_block, int cap = 4096) {
 
 }  // namespace
 
-#define REQUIRE(cond, who)                                 \
-  if (!(cond)) {                                           \
-    set_error(who ": bad arguments (" #cond ")");          \
-    return PGCA_ERR_INVALID;                               \
-  }
-
 extern "C" int pgca_patchify(const float* pixels, int32_t B, int32_t image, int32_t patch, int32_t ld_out,
                              void* out_bf16, void* stream) {
   const int D = 3 * patch * patch;

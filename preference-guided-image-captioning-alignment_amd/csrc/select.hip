@@ -554,12 +554,6 @@ __global__ __launch_bounds__(SEL_THREADS) void select_beam_kernel(
   }
 }
 
-#define REQUIRE(cond, who)                        \
-  if (!(cond)) {                                  \
-    set_error(who ": bad arguments (" #cond ")"); \
-    return PGCA_ERR_INVALID;                      \
-  }
-
 constexpr size_t SEL_MAX_DYN_LDS = 60 * 1024;
 
 }  // namespace
@@ -570,8 +564,6 @@ using namespace pgca;
 namespace {
 const pgca_select_opts NO_OPTS = {0, 0, nullptr};
 }
-
-extern "C" int pgca_sizeof_select_opts(void) { return (int)sizeof(pgca_select_opts); }
 
 extern "C" int pgca_select_token_ex(const float* logits, int32_t ld, int32_t V, int32_t R, const int64_t* prev,
                                     int32_t ld_prev, int32_t n_prev, float repetition_penalty, float temperature,

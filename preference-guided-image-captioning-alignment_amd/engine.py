@@ -24,15 +24,15 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import hip
+from . import abi, hip
 from .arch import GptArch, ModelArch, VitArch
 from .params import ParamStore, Segment, VOCAB_TILE
 
 logger = logging.getLogger(__name__)
 
 F32, BF16, I32, I64 = torch.float32, torch.bfloat16, torch.int32, torch.int64
-ATTN_BWD_MAX_S = 1024        # include/pgca_hip.h PGCA_ATTN_SPLIT_MAX_S
-ATTN_BWD_ONEPASS_MAX_S = 512  # include/pgca_hip.h PGCA_ATTN_MAX_S
+ATTN_BWD_MAX_S = abi.CONSTANTS["PGCA_ATTN_SPLIT_MAX_S"]
+ATTN_BWD_ONEPASS_MAX_S = abi.CONSTANTS["PGCA_ATTN_MAX_S"]
 
 
 def attention_backward(qkv, out, dout, lse, key_mask, B, S, heads, causal, dqkv, drop=None, cu=None):

@@ -17,6 +17,8 @@ from typing import Callable, Iterable, Iterator
 
 import torch
 
+from . import abi
+
 _STOP = object()
 
 PRECISION_BITS = 32 - 8 - 2     # Pillow src/libImaging/Resample.c
@@ -183,7 +185,7 @@ class GpuImageProcessor:
 
 
 # ----------------------------------------------------------------------------------------------- training transform
-TRAIN_PARAM_INTS = 20       # include/pgca_hip.h pgca_image_train_transform
+TRAIN_PARAM_INTS = abi.CONSTANTS["PGCA_TRAIN_PARAM_INTS"]
 
 
 def _fix16(v: float) -> int:

@@ -1,20 +1,17 @@
-"""C-ABI surface checks that need no GPU: the library builds/loads and exports exactly the
-entry points include/pgca_hip.h declares; the ctypes struct mirrors the C struct."""
+"""C-ABI surface checks that need no GPU: the library builds/loads and exports exactly the entry points
+include/pgca_hip.h declares; what the binding derives from the header (``pgca_amd.abi``: prototypes, structs, the
+scalar mapping) is what a C++ compiler reads in it."""
 import ctypes
 import os
-import re
+import shutil
 import subprocess
 
 import pytest
 import torch  # noqa: F401  (loads libamdhip64 first, as the product does)
 
-from pgca_amd import REPO_ROOT, hip
+from pgca_amd import REPO_ROOT, abi, hip
 
-
-def header_functions():
-    src = open(os.path.join(REPO_ROOT, "include", "pgca_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(pgca_[a-z0-9_]+)\s*\(", src)))
+INCLUDE = os.path.join(REPO_ROOT, "include")
 
 
 @pytest.fixture(scope="module")
@@ -26,11 +23,14 @@ def lib():
 
 
 def test_every_declared_symbol_is_exported(lib):
-    declared = header_functions()
-    assert len(declared) >= 30
+    """Header and library name the same entry points, in both directions."""
+    declared = sorted(abi.PROTOTYPES)
+    assert len(declared) >= 30 and declared == sorted(hip.EXPORTS)
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in pgca_hip.h but not exported"
-    assert sorted(hip.EXPORTS) == declared, set(hip.EXPORTS) ^ set(declared)
+    nm = subprocess.run(["nm", "-D", "--defined-only", hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = sorted(ln.split()[-1] for ln in nm.splitlines() if ln.split()[-1].startswith("pgca_"))
+    assert exported == declared, set(exported) ^ set(declared)
 
 
 def test_version_and_error_string(lib):
@@ -38,35 +38,70 @@ def test_version_and_error_string(lib):
     assert isinstance(lib.pgca_last_error(), bytes)
 
 
-def test_gemm_args_layout_matches_c_struct(tmp_path):
-    """Compile a tiny C program against the header and compare sizeof/offsetof with ctypes."""
-    fields = [f[0] for f in hip.GemmArgs._fields_]
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "pgca_hip.h"\nint main(){printf("%zu", sizeof(pgca_gemm_args));'
+def abi_check_source(prototypes):
+    """A C++ translation unit that compiles exactly when the header says what the reader's tables say: one assertion on
+    the function type of every entry, offset and size of every struct field against the ctypes structure, and size,
+    signedness and float/integer kind of every mapped scalar type.  Returns (source, entries, structs)."""
+    out = ["#include <cstddef>", "#include <type_traits>", '#include "pgca_hip.h"']
+    for name, p in prototypes.items():
+        fn = f"{p.ret} (*)({', '.join(t for t, _ in p.params)})"
+        out.append(f'static_assert(std::is_same_v<decltype(&{name}), {fn}>, "{name}");')
+    for name, st in abi.STRUCTS.items():
+        out.append(f'static_assert(sizeof({name}) == {ctypes.sizeof(st)}, "sizeof {name}");')
+        for field, ctype in st._fields_:
+            out.append(f"static_assert(offsetof({name}, {field}) == {getattr(st, field).offset} && "
+                       f'sizeof({name}::{field}) == {ctypes.sizeof(ctype)}, "{name}.{field}");')
+    for c, ctype in abi.SCALARS.items():
+        is_float, is_signed = isinstance(ctype(0).value, float), ctype(-1).value < 0
+        out.append(f"static_assert(sizeof({c}) == {ctypes.sizeof(ctype)} && std::is_floating_point_v<{c}> == "
+                   f'{str(is_float).lower()} && std::is_signed_v<{c}> == {str(is_signed).lower()}, "{c}");')
+    out.append(f'static_assert(sizeof(void*) == {ctypes.sizeof(ctypes.c_void_p)} && sizeof(const char*) == '
+               f'{ctypes.sizeof(ctypes.c_char_p)}, "pointers");')
+    return "\n".join(out) + "\n", len(prototypes), len(abi.STRUCTS)
+
+
+def test_the_compiler_reads_the_header_as_the_binding_does(tmp_path):
+    cxx = shutil.which("g++") or "/opt/rocm/llvm/bin/clang++"
+
+    def compiles(source, stem):
+        f = tmp_path / (stem + ".cpp")
+        f.write_text(source)
+        return subprocess.run([cxx, "-std=c++17", "-fsyntax-only", "-I", INCLUDE, str(f)], capture_output=True, text=True)
+
+    source, entries, structs = abi_check_source(abi.PROTOTYPES)
+    assert entries >= 58 and structs >= 3 and source.count("decltype(&pgca_") == entries
+    assert sum(len(st._fields_) for st in abi.STRUCTS.values()) >= 35 + 21 + 3
+    ok = compiles(source, "abi")
+    assert ok.returncode == 0, ok.stderr
+    # one parameter type of one entry altered (each a mistake that would load, run and corrupt silently): refused
+    for entry, index, wrong in (("pgca_adamw", 7, "int32_t"), ("pgca_attention_fwd", 8, "int32_t"),
+                                ("pgca_sqnorm", 1, "int32_t"), ("pgca_dpo_loss", 0, "const void*")):
+        p = abi.PROTOTYPES[entry]
+        assert p.params[index][0] != wrong
+        params = list(p.params)
+        params[index] = (wrong, params[index][1])
+        bad = compiles(abi_check_source({**abi.PROTOTYPES, entry: p._replace(params=params)})[0], "bad_" + entry)
+        assert bad.returncode != 0 and entry in bad.stderr, (entry, bad.stderr)
+
+
+@pytest.mark.parametrize("name", sorted(abi.STRUCTS))
+def test_struct_layout_matches_c_struct(tmp_path, lib, name):
+    """Compile a tiny C program against the header and compare sizeof/offsetof with ctypes and with the library."""
+    st = abi.STRUCTS[name]
+    assert st in (hip.GemmArgs, hip.SkinnyArgs, hip.SelectOpts)
+    fields = [f[0] for f in st._fields_]
+    prog = f'#include <stdio.h>\n#include <stddef.h>\n#include "pgca_hip.h"\nint main(){{printf("%zu", sizeof({name}));'
     for f in fields:
-        prog += f'printf(" %zu", offsetof(pgca_gemm_args, {f}));'
+        prog += f'printf(" %zu", offsetof({name}, {f}));'
     prog += "return 0;}\n"
     c = tmp_path / "o.c"
     c.write_text(prog)
     exe = tmp_path / "o"
-    subprocess.run(["gcc", "-I", os.path.join(REPO_ROOT, "include"), str(c), "-o", str(exe)], check=True)
+    subprocess.run(["gcc", "-I", INCLUDE, str(c), "-o", str(exe)], check=True)
     nums = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert nums[0] == ctypes.sizeof(hip.GemmArgs)
-    assert nums[1:] == [getattr(hip.GemmArgs, f).offset for f in fields]
-
-
-def test_skinny_args_layout_matches_c_struct(tmp_path):
-    fields = [f[0] for f in hip.SkinnyArgs._fields_]
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "pgca_hip.h"\nint main(){printf("%zu", sizeof(pgca_skinny_args));'
-    for f in fields:
-        prog += f'printf(" %zu", offsetof(pgca_skinny_args, {f}));'
-    prog += "return 0;}\n"
-    c = tmp_path / "s.c"
-    c.write_text(prog)
-    exe = tmp_path / "s"
-    subprocess.run(["gcc", "-I", os.path.join(REPO_ROOT, "include"), str(c), "-o", str(exe)], check=True)
-    nums = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert nums[0] == ctypes.sizeof(hip.SkinnyArgs)
-    assert nums[1:] == [getattr(hip.SkinnyArgs, f).offset for f in fields]
+    assert nums[0] == ctypes.sizeof(st) == getattr(lib, name.replace("pgca_", "pgca_sizeof_"))()
+    assert nums[1:] == [getattr(st, f).offset for f in fields]
+    assert lib.pgca_version() == hip.ABI_VERSION == 306
 
 
 def test_host_side_argument_validation_needs_no_gpu(lib):

@@ -8,7 +8,7 @@ import re
 import pytest
 import torch  # noqa: F401  (loads libamdhip64 first, as the product does)
 
-from pgca_amd import REPO_ROOT, hip
+from pgca_amd import REPO_ROOT, abi, hip
 
 
 @pytest.fixture(scope="module")
@@ -24,10 +24,8 @@ def header():
 
 
 def prototype(name):
-    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-    assert m, f"{name} has no prototype in pgca_hip.h"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
+    assert abi.PROTOTYPES[name].ret == "int", f"{name} has no status-returning prototype in pgca_hip.h"
+    return [f"{t} {n}" for t, n in abi.PROTOTYPES[name].params]
 
 
 def test_split_entry_is_declared_exported_and_bound(lib):

@@ -3,12 +3,11 @@
 entry and of ``pgca_set_option``, the option the pair adds, and the argument checks that run before any launch."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch  # noqa: F401  (loads libamdhip64 first, as the product does)
 
-from pgca_amd import REPO_ROOT, hip
+from pgca_amd import REPO_ROOT, abi, hip
 
 
 @pytest.fixture(scope="module")
@@ -20,11 +19,8 @@ def lib():
 
 
 def prototype(name):
-    src = open(os.path.join(REPO_ROOT, "include", "pgca_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-    assert m, f"{name} has no prototype in pgca_hip.h"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
+    assert abi.PROTOTYPES[name].ret == "int", f"{name} has no status-returning prototype in pgca_hip.h"
+    return [f"{t} {n}" for t, n in abi.PROTOTYPES[name].params]
 
 
 def test_grouped_entry_prototype_export_and_ctypes_agree(lib):
