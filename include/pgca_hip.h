@@ -390,6 +390,20 @@ int pgca_seq_pack_prepare(int32_t* mask32, int32_t Bq, int32_t S, int32_t pad_to
  * (the DLOGITS epilogue computes the cross-entropy form softmax - onehot, so it is fed -dLoss/dtok_lp). */
 int pgca_row_scale(const float* dseq, const int32_t* seq_of_row, const int32_t* seq_count, int32_t nrows,
                    int32_t mode, float* row_scale, void* stream);
+/* Language-model loss head over the compact rows (reference CaptionDecoder.forward(labels=...), model.py:561-619: HF's
+ * ForCausalLMLoss, here over the scored tokens).  Row r counts iff seq_of_row == NULL or seq_of_row[r] < seq_limit; with
+ * n counted rows, loss[0] = -(sum of the counted tok_lp) / n (n == 0: 0/0 = NaN, as the mean of pgca_seq_reduce).
+ * metrics[4] (optional) = {sum of -tok_lp, n, loss, 1 if the loss is finite else 0}, all on the device (no host sync).
+ * row_coef[nrows] (optional) = -dLoss/d tok_lp * grad_scale, the form the DLOGITS epilogue takes (pgca_row_scale with
+ * mode bit 2): grad_scale / n on counted rows, 0 elsewhere.  accumulate 0 writes every element (all exactly 0 when the
+ * loss is not finite, the rule of pgca_dpo_loss); accumulate 1 adds to the counted rows (nothing when it is not finite).
+ * One workgroup; the sum is carried in double in a fixed order (two launches on one input are bitwise equal) and the
+ * loss is rounded to f32 once.  LIMIT: sized for the compact rows of one micro-batch, nrows up to ~1e5 (12 us at 36 k
+ * rows on an MI355X); the one workgroup makes two serial passes, so time grows linearly with nrows and nothing is spread
+ * over the other CUs - a caller with millions of rows needs a different kernel, not this entry.  tok_lp is read in 16-byte vectors from its first 16-byte boundary when seq_of_row is
+ * aligned at the same row, else row by row; any nrows >= 1. */
+int pgca_token_nll(const float* tok_lp, const int32_t* seq_of_row, int32_t seq_limit, int32_t nrows, float grad_scale,
+                   int32_t accumulate, float* loss, float* row_coef, float* metrics, void* stream);
 
 /* ------------------------------------------------------------------ pooling / normalise (Stage 1) */
 /* pooled[b] = sum_s feats[b,s]*mask[b,s] / max(sum_s mask, 1)  (model.py:449-456); feats f32.

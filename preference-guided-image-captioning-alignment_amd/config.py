@@ -14,7 +14,12 @@ import yaml
 REQUIRED_SECTIONS = ("model", "training")
 
 MI355X_DEFAULTS = {
-    "dpo": {"reference_free": True, "label_smoothing": 0.0},   # True = the reference trainer's 2-forward loss
+    # reference_free True = the reference trainer's 2-forward loss; sft_alpha > 0 adds sft_alpha * NLL(chosen) to the loss
+    "dpo": {"reference_free": True, "label_smoothing": 0.0, "sft_alpha": 0.0},
+    # what Stage 2 trains on: "dpo" (as the reference), "caption" (the LM loss of steps.CaptionStep on the chosen captions)
+    # or "caption_then_dpo" (caption phase, then DPO whose frozen reference policy is the captioner just trained);
+    # caption_learning_rate: the caption phase's rate (null = training.stage2.learning_rate)
+    "stage2": {"objective": "dpo", "caption_learning_rate": None},
     "stage1": {"global_negatives": False},                      # False = local negatives, as the reference
     "allreduce_bucket_elems": 64 * 1024 * 1024,
     "allreduce_layer_group": 4,
@@ -52,6 +57,26 @@ def select_recompute(config) -> str:
     if mode not in RECOMPUTE_MODES:
         raise ValueError(f"mi355x.recompute must be one of {RECOMPUTE_MODES}, got {mode!r}")
     return mode
+
+
+STAGE2_OBJECTIVES = ("dpo", "caption", "caption_then_dpo")
+
+
+def select_objective(config) -> str:
+    """``mi355x.stage2.objective`` of a ``Config`` or a plain nested dict (absent: ``"dpo"``, so the reference's configs
+    select what they always did); anything but ``STAGE2_OBJECTIVES`` is a ``ValueError`` naming the key."""
+    cur = getattr(config, "config", config)
+    for key in ("mi355x", "stage2", "objective"):
+        cur = cur.get(key) if isinstance(cur, dict) else None
+    mode = MI355X_DEFAULTS["stage2"]["objective"] if cur is None else cur
+    if mode not in STAGE2_OBJECTIVES:
+        raise ValueError(f"mi355x.stage2.objective must be one of {STAGE2_OBJECTIVES}, got {mode!r}")
+    return mode
+
+
+def checkpoint_objective(ck: dict) -> str:
+    """The Stage-2 objective a checkpoint dict was written under; one from before the key existed counts as ``"dpo"``."""
+    return ck.get("mi355x_state", {}).get("objective", "dpo")
 
 
 GENERATE_KEYS = {"max_length": int, "num_beams": int, "temperature": float, "do_sample": bool, "top_p": float,

@@ -174,6 +174,71 @@ __global__ void dpo_loss_kernel(const float* __restrict__ pw, const float* __res
   }
 }
 
+// Token-mean NLL over the compact scored rows (HF ForCausalLMLoss on the kept tokens) and its per-row seed for the DLOGITS
+// epilogue.  ONE workgroup of 16 waves: a micro-batch has at most ~1e5 compact rows (0.4 MB), which sixteen waves read
+// in a few microseconds, and a single workgroup needs no partial buffer between launches.  The sum is carried in double
+// (thread -> wave shuffles -> the 16 wave partials added in wave order by thread 0) and rounded to f32 once, after the
+// division, so the order is fixed and the result is within one f32 rounding of the exact mean.
+// Rows [0, head) and [head + 4*nvec, nrows) are read one by one, the rows between as 16-byte vectors (the launcher picks
+// head so that both arrays are aligned there, or head = nrows).  Row r counts iff seq == NULL or seq[r] < seq_limit.
+constexpr int NLL_THREADS = 1024;
+__global__ __launch_bounds__(NLL_THREADS) void token_nll_kernel(const float* __restrict__ tok, const int* __restrict__ seq,
+                                                                int seq_limit, int nrows, int head, int nvec,
+                                                                float grad_scale, int accumulate, float* __restrict__ loss,
+                                                                float* __restrict__ coef, float* __restrict__ metrics) {
+  __shared__ double red_s[NLL_THREADS / 64];
+  __shared__ int red_n[NLL_THREADS / 64];
+  __shared__ float s_coef;
+  __shared__ int s_live;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  double s = 0.0;
+  int n = 0;
+  for (int r = tid; r < head; r += NLL_THREADS)
+    if (!seq || seq[r] < seq_limit) { s += (double)tok[r]; ++n; }
+  for (int i = tid; i < nvec; i += NLL_THREADS) {
+    const float4 v = *reinterpret_cast<const float4*>(tok + head + 4 * (size_t)i);
+    int4 q = make_int4(0, 0, 0, 0);
+    if (seq) q = *reinterpret_cast<const int4*>(seq + head + 4 * (size_t)i);
+    if (!seq || q.x < seq_limit) { s += (double)v.x; ++n; }
+    if (!seq || q.y < seq_limit) { s += (double)v.y; ++n; }
+    if (!seq || q.z < seq_limit) { s += (double)v.z; ++n; }
+    if (!seq || q.w < seq_limit) { s += (double)v.w; ++n; }
+  }
+  for (int r = head + 4 * nvec + tid; r < nrows; r += NLL_THREADS)
+    if (!seq || seq[r] < seq_limit) { s += (double)tok[r]; ++n; }
+  s = wave_sum(s);
+  n = wave_sum(n);
+  if (lane == 0) { red_s[w] = s; red_n[w] = n; }
+  __syncthreads();
+  if (tid == 0) {
+    double ts = 0.0;
+    int tn = 0;
+    for (int k = 0; k < NLL_THREADS / 64; ++k) { ts += red_s[k]; tn += red_n[k]; }
+    const float l = (float)(-ts / (double)tn);  // tn == 0: 0/0 = NaN, as the mean of pgca_seq_reduce
+    const bool live = isfinite(l);
+    loss[0] = l;
+    if (metrics) {
+      metrics[0] = (float)(-ts);
+      metrics[1] = (float)tn;
+      metrics[2] = l;
+      metrics[3] = live ? 1.f : 0.f;
+    }
+    s_coef = live ? grad_scale / (float)tn : 0.f;
+    s_live = live;
+  }
+  __syncthreads();
+  if (!coef || (accumulate && !s_live)) return;  // a non-finite loss adds nothing / writes zeros below
+  const float c = s_coef;
+  for (int r = tid; r < nrows; r += NLL_THREADS) {
+    const bool counted = s_live && (!seq || seq[r] < seq_limit);
+    if (accumulate) {
+      if (counted) coef[r] += c;
+    } else {
+      coef[r] = counted ? c : 0.f;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------ batch index preparation
 // The integer work of the loss (reference model.py:1069-1083 / components.py:340-357: shift, mask product, gather index)
 // on the device, so a batch needs no host pass: rows (b, t) with mask[b, t+1] != 0 are kept, sorted by sequence;
@@ -657,6 +722,22 @@ extern "C" int pgca_dpo_loss(const float* pol_w, const float* pol_l, const float
   hipLaunchKernelGGL(dpo_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pol_w, pol_l, ref_w, ref_l, B, beta,
                      label_smoothing, loss, dpol_w, dpol_l, metrics);
   return check_launch("pgca_dpo_loss");
+}
+
+extern "C" int pgca_token_nll(const float* tok_lp, const int32_t* seq_of_row, int32_t seq_limit, int32_t nrows,
+                              float grad_scale, int32_t accumulate, float* loss, float* row_coef, float* metrics,
+                              void* stream) {
+  REQUIRE(tok_lp && loss && nrows > 0 && seq_limit >= 0 && (accumulate == 0 || accumulate == 1) &&
+              (((uintptr_t)tok_lp & 3) == 0) && (((uintptr_t)seq_of_row & 3) == 0),
+          "pgca_token_nll");
+  // rows before the first 16-byte boundary of tok_lp are read one by one; the vector body needs seq_of_row aligned at
+  // the same row, otherwise every row is read alone
+  int head = (int)((16 - ((uintptr_t)tok_lp & 15)) & 15) / 4;
+  if (head > nrows || (seq_of_row && (((uintptr_t)(seq_of_row + head)) & 15) != 0)) head = nrows;
+  const int nvec = (nrows - head) / 4;
+  hipLaunchKernelGGL(token_nll_kernel, dim3(1), dim3(NLL_THREADS), 0, (hipStream_t)stream, tok_lp, seq_of_row, seq_limit,
+                     nrows, head, nvec, grad_scale, accumulate, loss, row_coef, metrics);
+  return check_launch("pgca_token_nll");
 }
 
 extern "C" int pgca_masked_mean_fwd(const float* feats, const int32_t* mask, int32_t B, int32_t S, int32_t H,

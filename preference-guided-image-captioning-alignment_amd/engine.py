@@ -659,6 +659,16 @@ class GptTrunk:
         drop = self.saved.get("drop") if self.saved else None
         return drop(len(self.layers) - 1, KIND_RESID_MLP) if drop is not None else None
 
+    def skip_backward(self) -> None:
+        """A backward that is NOT launched (the step found its loss not finite, so the micro-batch adds nothing) still owes
+        what every rank's backward does besides arithmetic: the per-layer gradient hook, fired for every layer in the
+        backward's order, so that a data-parallel reducer issues the same collectives on a rank that skips as on one that
+        does not.  The saved activations are dropped."""
+        if self.grad_hook is not None:
+            for li in range(len(self.layers) - 1, -1, -1):
+                self.grad_hook(li)
+        self.saved = None
+
     def backward(self, g: torch.Tensor, g_bf: torch.Tensor) -> torch.Tensor:
         """g / g_bf: dL/d(stream after last block) as f32 and bf16 [M, H]. Returns dL/dh0 (f32).
         Weight/bias/LN gradients are ACCUMULATED into the segment's flat gradient buffer.
@@ -1021,6 +1031,7 @@ class CaptionDecoderEngine:
         self.ow, self.ob = _P(seg, p + ".cross_attention.out_proj.weight"), _P(seg, p + ".cross_attention.out_proj.bias")
         self.anw, self.anb = _P(seg, p + ".attention_norm.weight"), _P(seg, p + ".attention_norm.bias")
         self.saved = None
+        self.tok_lp: Optional[torch.Tensor] = None
         self._dec: Optional[DecodeState] = None   # the decode in flight (decode_begin)
         self._graphs: dict = {}                   # captured decode steps (decode_advance)
         self.graph_captures = 0                   # steps captured into a graph / steps served by replaying one
@@ -1106,6 +1117,7 @@ class CaptionDecoderEngine:
         hip.rowstats_combine(smax, ssum, nparts, 2 * ((self.V + 127) // 128), tval, Mc, lse=lse, out_logprob=tok)
         if save:
             self.saved.update(hf=hf, mf=mf, rf=rf, lse=lse)
+        self.tok_lp = tok   # the last forward's, for a token-level loss head on top of a sequence-level one (steps)
         return tok
 
     def sequence_logprobs(self, emb: torch.Tensor, sb: SeqBatch, reduce: str, save: bool, drop=None,
@@ -1289,8 +1301,25 @@ class CaptionDecoderEngine:
         return out[:, :self.V]
 
     # -- backward -------------------------------------------------------------------------------
-    def backward(self, dseq: torch.Tensor) -> torch.Tensor:
-        """dseq [Bq] = dLoss/dseq_lp.  Accumulates all decoder gradients; returns dLoss/demb [Bq, P] f32."""
+    def row_coef(self, dseq: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The per-row operand of the LM-head backward, [Mc] f32 = -dLoss/d tok_lp of the saved forward's compact rows:
+        the engine's own buffer, filled from ``dseq`` [Bq] = dLoss/dseq_lp when given (``pgca_row_scale``), else handed
+        out as it is for a loss head to write (``pgca_token_nll``) or to add to."""
+        s = self.saved
+        sb: SeqBatch = s["sb"]
+        rs = self._buf("row_scale", (sb.n_rows,), F32)
+        if dseq is not None:
+            # d tok_lp / d logits = onehot - softmax; the DLOGITS epilogue computes the cross-entropy form
+            # row_scale * (softmax - onehot), so it is fed -dLoss/dtok_lp (mode bit 2 negates)
+            hip.row_scale(dseq, sb.seq_of_row, sb.counts, sb.n_rows, (1 if s["reduce"] == "mean" else 0) | 2, rs)
+        return rs
+
+    def backward(self, dseq: Optional[torch.Tensor] = None, row_coef: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dseq [Bq] = dLoss/dseq_lp, or ``row_coef`` [Mc] = -dLoss/d tok_lp per compact row, ready for the DLOGITS
+        epilogue (a token-level loss; a term on top of a sequence-level one is added to ``self.row_coef(dseq)`` first).
+        Accumulates all decoder gradients; returns dLoss/demb [Bq, P] f32."""
+        if (dseq is None) == (row_coef is None):
+            raise ValueError("backward takes dseq or row_coef, one of them")
         s = self.saved
         sb: SeqBatch = s["sb"]
         a = self.arch.gpt
@@ -1299,10 +1328,7 @@ class CaptionDecoderEngine:
         rw = _rows(pack, Bq, S)
         M = rw.M
         ws = self.ws
-        rs = self._buf("row_scale", (Mc,), F32)
-        # d tok_lp / d logits = onehot - softmax; the DLOGITS epilogue computes the cross-entropy form
-        # row_scale * (softmax - onehot), so it is fed -dLoss/dtok_lp (mode bit 2 negates)
-        hip.row_scale(dseq, sb.seq_of_row, sb.counts, Mc, (1 if s["reduce"] == "mean" else 0) | 2, rs)
+        rs = self.row_coef(dseq) if row_coef is None else row_coef
         # LM head: dlogits recomputed tile by tile in row chunks
         dhf = self._buf("dhf32", (Mc, H), F32, zero=True)  # f32 + accumulate: lets the K = vocab dgrad GEMM split K
         ck = min(self.LM_CHUNK, Mc)

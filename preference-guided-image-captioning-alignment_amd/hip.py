@@ -389,6 +389,13 @@ def row_scale(dseq, seq_of_row, seq_count, nrows, mode, out):
     _call("pgca_row_scale", dseq, seq_of_row, seq_count, nrows, mode, out)
 
 
+def token_nll(tok_lp, seq_of_row, seq_limit, nrows, grad_scale, accumulate, loss, row_coef=None, metrics=None):
+    """Token-mean NLL of the compact rows of sequences < ``seq_limit`` (all rows when ``seq_of_row`` is None) and its
+    per-row DLOGITS coefficient; see pgca_hip.h."""
+    _call("pgca_token_nll", tok_lp, seq_of_row, seq_limit, nrows, grad_scale, 1 if accumulate else 0, loss, row_coef,
+          metrics)
+
+
 def masked_mean_fwd(feats, mask, B, S, H, pooled, cu=None):
     _call("pgca_masked_mean_fwd", feats, mask, B, S, H, pooled, cu)
 

@@ -198,7 +198,12 @@ class CaptionDecoder:
         loss = None
         if labels is not None:  # HF ForCausalLMLoss: mean CE over all shifted positions (modeling_gpt2.py:700-716)
             B, S, V = logits.shape
-            full = make_seq_batch(labels, torch.ones_like(labels), dev, pack=False)
+            # ... that do not carry the ignore index: a label of -100 leaves its position out of the mean (and is never
+            # used as a gather index); labels without one keep every position, whatever the attention mask says
+            keep = (labels != -100).to(labels.dtype)
+            if not bool(keep[:, 1:].any()):      # every shifted label ignored: the mean over nothing, NaN as HF returns it
+                return DecoderOutput(logits=logits, loss=torch.full((), float("nan"), dtype=F32, device=dev))
+            full = make_seq_batch(labels * keep, keep, dev, pack=False)
             tok = torch.empty(full.n_rows, dtype=F32, device=dev)
             hip.logits_logprob(logits, V, V, full.row_map, full.targets, full.n_rows, tok)
             loss = -tok.mean()

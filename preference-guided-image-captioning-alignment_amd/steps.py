@@ -4,6 +4,9 @@
                       chosen+rejected batched along M, optional frozen reference policy (4-forward DPO,
                       components.py:192-249) or the trainer's reference-free 2-forward PreferenceLoss
                       (model.py:1038-1050), backward through the policy only.
+* ``CaptionStep``     the caption decoder's language-model loss (reference model.py:561-619, 838-851:
+                      ``generation_loss``) over the scored tokens of one caption per image, backward through the
+                      decoder and the vision head; ``DPOStep(sft_alpha=a)`` adds a times the same loss on the chosen.
 * ``ContrastiveStep`` Stage 1 (trainer.py:464-520): frozen ViT + head, GPT-2 text tower + head,
                       F.normalize, NT-Xent, backward.
 * ``FusedOptimizer``  AdamW + global-norm clip + cosine warm-up (trainer.py:275-289,511-520) with the
@@ -120,7 +123,7 @@ class DPOStep:
                  dec: CaptionDecoderEngine, beta: float = 0.1, reference_free: bool = False,
                  label_smoothing: float = 0.0, reduce: Optional[str] = None, ref: Optional[ReferencePolicy] = None,
                  ref_side_stream: bool = False, dropout: Optional[DropoutPlan] = None, packed: bool = True,
-                 recompute: str = "none"):
+                 recompute: str = "none", sft_alpha: float = 0.0):
         self.store, self.ws, self.vit, self.vhead, self.dec = store, ws, vit, vhead, dec
         # activation recompute of the policy trunk's training forward / backward (engine.GptTrunk.recompute); the frozen
         # reference policy and every evaluation forward keep nothing anyway
@@ -134,6 +137,13 @@ class DPOStep:
         dev = ws.device
         self.loss = torch.zeros(1, dtype=F32, device=dev)
         self.metrics = torch.zeros(4, dtype=F32, device=dev)
+        # loss = DPO + sft_alpha * NLL of the chosen captions (token mean over the rows of sequences < B); 0 = DPO alone,
+        # on the code path and launch sequence it always had
+        self.sft_alpha = float(sft_alpha)
+        if self.sft_alpha < 0:
+            raise ValueError(f"sft_alpha must be >= 0, got {sft_alpha}")
+        self.nll = torch.zeros(1, dtype=F32, device=dev)           # the NLL term alone
+        self.nll_metrics = torch.zeros(4, dtype=F32, device=dev)   # pgca_token_nll: sum -tok_lp, tokens, loss, finite
         self._ref_stream = None
         self.ref_side_stream = bool(ref_side_stream)
         # train-mode dropout of the policy (the frozen reference policy always runs without dropout)
@@ -210,7 +220,14 @@ class DPOStep:
                      B, self.beta, self.ls, self.loss, dseq[:B], dseq[B:], self.metrics)
         if loss_scale != 1.0:
             dseq.mul_(loss_scale)
-        demb2 = self.dec.backward(dseq)
+        if self.sft_alpha == 0.0:
+            demb2 = self.dec.backward(dseq)
+        else:
+            rs = self.dec.row_coef(dseq)                      # the DPO term's row coefficients ...
+            self._add_nll(sb, B, self.sft_alpha * loss_scale, rs)   # ... plus the NLL term's, on the chosen rows
+            # either term non-finite -> the sum is, and the micro-batch adds nothing (each kernel zeroes only its own)
+            rs.mul_(torch.isfinite(self.loss).to(F32))
+            demb2 = self.dec.backward(row_coef=rs)
         demb = self.ws.get("dpo.demb", (B, self.store.arch.proj_dim), F32)
         torch.add(demb2[:B], demb2[B:], out=demb)
         dpooled = self.vhead.backward(demb, need_dx=self.vit.trainable)
@@ -224,6 +241,86 @@ class DPOStep:
         pol, ref_lp = self.forward(images, sb, False)
         hip.dpo_loss(pol[:B], pol[B:], None if ref_lp is None else ref_lp[:B], None if ref_lp is None else ref_lp[B:],
                      B, self.beta, self.ls, self.loss, None, None, self.metrics)
+        if self.sft_alpha != 0.0:
+            self._add_nll(sb, B, 0.0, None)
+        return self.loss
+
+    def _add_nll(self, sb: SeqBatch, B: int, grad_scale: float, row_coef: Optional[torch.Tensor]) -> None:
+        """``self.loss += sft_alpha * NLL`` of the chosen captions (the compact rows of sequences < B of the last policy
+        forward), its row coefficients added to ``row_coef``."""
+        hip.token_nll(self.dec.tok_lp, sb.seq_of_row, B, sb.n_rows, grad_scale, True, self.nll, row_coef,
+                      self.nll_metrics)
+        hip.axpy(self.nll, self.sft_alpha, self.loss, 1, accumulate=True)
+
+
+class CaptionStep:
+    """Caption (SFT) micro-step: the language-model loss of the decoder on one caption per image - what the reference
+    hands out as ``generation_loss`` when ``labels`` are passed (model.py:561-619, 838-851) - with its gradients
+    accumulated into the flat buffers of the vision head, the decoder and (when trainable) the ViT.
+
+    The loss is the token mean over the SCORED positions of the micro-batch (target ``ids[b, t+1]`` where
+    ``mask[b, t+1] == 1``, the rule of ``pgca_seq_batch_prepare``): padded positions are left out, unlike the surface's
+    ``generation_loss``, which keeps HF's mean over every shifted position of the labels it is given."""
+
+    def __init__(self, store: ParamStore, ws: Workspace, vit: VisionTower, vhead: ProjHead,
+                 dec: CaptionDecoderEngine, dropout: Optional[DropoutPlan] = None, packed: bool = True,
+                 recompute: str = "none"):
+        self.store, self.ws, self.vit, self.vhead, self.dec = store, ws, vit, vhead, dec
+        dec.trunk.recompute = recompute
+        dev = ws.device
+        self.loss = torch.zeros(1, dtype=F32, device=dev)
+        self.metrics = torch.zeros(4, dtype=F32, device=dev)   # sum of -tok_lp, scored tokens, loss, finite flag
+        self.dropout = dropout if dropout is not None else DropoutPlan(0.0)
+        self.packed = bool(packed)
+
+    @staticmethod
+    def prepare(batch: dict, device) -> dict:
+        """One caption per image: ``caption_ids`` / ``caption_mask`` when the batch has them, else the chosen side of a
+        Stage-2 batch (``preferred_ids`` / ``preferred_mask``), so a preference loader feeds this step unchanged."""
+        key = "caption" if "caption_ids" in batch else "preferred"
+        ids, mask = batch[key + "_ids"], batch[key + "_mask"]
+        image = batch["image"].to(device, F32, non_blocking=True)
+        return {"image": image, "seq": make_seq_batch(ids, mask, device)}
+
+    def forward(self, images: torch.Tensor, sb: SeqBatch, save: bool = True) -> torch.Tensor:
+        """Token log-probs of the scored rows, [sb.n_rows] f32."""
+        B = images.shape[0]
+        assert sb.Bq == B
+        _, _, pooled_bf = self.vit.forward(images, save)
+        plan = self.dropout
+        plan.active = bool(save)
+        emb = self.vhead.forward(pooled_bf, B, save, plan.site(TOWER_VHEAD, 0, KIND_HEAD))
+        packed = self.packed and sb.pack is not None and sb.pack.Mp > 0
+        hL = self.dec.hidden(emb, sb, save, plan.bind(TOWER_DECODER), packed)
+        return self.dec.token_logprobs(hL, sb, save, packed)
+
+    def loss_and_grads(self, images: torch.Tensor, sb: SeqBatch, loss_scale: float = 1.0) -> torch.Tensor:
+        """Returns the (unscaled) loss as a 1-element device tensor; gradients of ``loss_scale * loss`` are accumulated.
+
+        A micro-batch whose loss is not finite adds exactly zero to every gradient buffer.  Zero seeds
+        (``pgca_token_nll``) are enough while the activations are finite, but a loss that is NaN because a weight is
+        would meet the NaN activations the forward saved in every gradient GEMM, and 0 * NaN is NaN: only a backward
+        that is not launched adds nothing.  So the finite flag of the metrics is read back once, after the forward (4
+        bytes; the one host wait of the step), and the backward is skipped - the trunk still fires its per-layer
+        gradient hooks, so the ranks of a data-parallel run keep issuing the same collectives."""
+        tok = self.forward(images, sb, True)
+        self.dropout.step += 1
+        rs = self.dec.row_coef()
+        hip.token_nll(tok, None, 0, sb.n_rows, loss_scale, False, self.loss, rs, self.metrics)
+        if float(self.metrics[3]) == 0.0:
+            self.dec.trunk.skip_backward()
+            self.dec.saved = None
+            return self.loss
+        demb = self.dec.backward(row_coef=rs)
+        dpooled = self.vhead.backward(demb, need_dx=self.vit.trainable)
+        if self.vit.trainable:
+            self.vit.backward(dpooled)
+        return self.loss
+
+    @torch.no_grad()
+    def loss_only(self, images: torch.Tensor, sb: SeqBatch) -> torch.Tensor:
+        tok = self.forward(images, sb, False)
+        hip.token_nll(tok, None, 0, sb.n_rows, 1.0, False, self.loss, None, self.metrics)
         return self.loss
 
 

@@ -15,7 +15,8 @@ semantics:
   dropped without an optimiser / scheduler step (the reference's ``zero_grad()`` is only real there); non-finite
   gradients skip the step (trainer.py:494-508).  All of it is decided ON THE DEVICE (gradient seeds zeroed by
   ``pgca_dpo_loss``, ``gate`` + all-reduced norm in ``pgca_step_control``): every rank takes the same decision and the
-  step loop never reads a loss back;
+  step loop never reads a loss back (the caption phase reads one flag per micro-batch: ``steps.CaptionStep`` does not
+  launch the backward of a micro-batch whose loss is not finite);
 * ``global_step`` counts micro-batches (trainer.py:525, 633).
 
 Differences (documented in DESIGN.md): no ``.item()`` per micro-batch (losses are read from the device every
@@ -35,12 +36,12 @@ from typing import Any, Dict, Iterable, List, Optional
 
 import torch
 
-from .config import select_recompute
+from .config import checkpoint_objective, select_objective, select_recompute
 from .dist import DataParallel, OverlappedTrunkReducer
 from .engine import DropoutPlan
 from .input import BatchPrefetcher
 from .model import PreferenceGuidedCaptioningModel
-from .steps import ContrastiveStep, DPOStep, FusedOptimizer, ReferencePolicy
+from .steps import CaptionStep, ContrastiveStep, DPOStep, FusedOptimizer, ReferencePolicy
 
 
 class PreferenceGuidedTrainer:
@@ -61,6 +62,10 @@ class PreferenceGuidedTrainer:
         self.beta = float(config.get("training.stage2.dpo_beta", 0.1))
         # mi355x.recompute, else the reference's hardware.gradient_checkpointing (config.select_recompute)
         self.recompute = select_recompute(config)
+        # what Stage 2 trains on: mi355x.stage2.objective = dpo | caption | caption_then_dpo (config.select_objective)
+        self.objective = select_objective(config)
+        self._phase = "dpo"                              # the phase of Stage 2 that is running: "caption" or "dpo"
+        self.reference_policy: Optional[ReferencePolicy] = None   # the frozen pi_ref of the last 4-forward DPO phase
         self.current_stage, self.global_step, self.epoch = 1, 0, 0
         self.best_val_loss, self.patience_counter = float("inf"), 0
         self._resume: Optional[Dict[str, Any]] = None   # optimiser / scheduler / dropout state of a loaded checkpoint
@@ -74,13 +79,20 @@ class PreferenceGuidedTrainer:
     def is_main_process(self) -> bool:
         return self.dp.rank == 0
 
+    def _resuming(self, stage: int) -> bool:
+        """A loaded checkpoint continues the phase that is about to start."""
+        r = self._resume
+        return r is not None and r.get("stage") == stage and (stage != 2 or r.get("phase", "dpo") == self._phase)
+
     def _dropout_plan(self, stage: int) -> DropoutPlan:
         """model.dropout (configs/default.yaml:22) at the reference's own train-mode sites and HF GPT-2's fixed 0.1 at
         its internal embd / attn / resid sites (``mi355x.gpt2_pdrop``); per-rank, per-stage seed."""
         seed = int(self.config.get("training.seed", 42)) * 1000 + stage * 100 + self.dp.rank
+        if stage == 2 and self._phase == "caption":
+            seed += 50                                   # the caption phase draws its own masks
         plan = DropoutPlan(float(getattr(self.model, "dropout", 0.0) or 0.0), base_seed=seed,
                            p_gpt=float(self.config.get("mi355x.gpt2_pdrop", 0.1)))
-        if self._resume is not None and self._resume.get("stage") == stage:
+        if self._resuming(stage):
             plan.step = int(self._resume.get("dropout_step", 0))
         self._plan = plan
         return plan
@@ -95,8 +107,8 @@ class PreferenceGuidedTrainer:
                                "(scripts/train.py truncates to a multiple of the world size)")
 
     # ------------------------------------------------------------------ optimiser
-    def _setup_optimizer(self, stage: int, num_training_steps: int) -> FusedOptimizer:
-        sc = self.config.get(f"training.stage{stage}")
+    def _setup_optimizer(self, stage: int, num_training_steps: int, sc: Optional[Dict[str, Any]] = None) -> FusedOptimizer:
+        sc = self.config.get(f"training.stage{stage}") if sc is None else sc
         # the CLIP tower joins when it was left trainable (reference AdamW(model.parameters()), trainer.py:275-281)
         names = ("vit", "vision_head", "text_tower", "text_head") if stage == 1 else ("vit", "vision_head", "decoder")
         segs = [self.model.store.segments[n] for n in names if self.model.store.segments[n].trainable]
@@ -104,7 +116,7 @@ class PreferenceGuidedTrainer:
                              betas=(0.9, 0.999), eps=1e-8, max_grad_norm=sc.get("max_grad_norm"),
                              warmup_steps=sc.get("warmup_steps", 0), total_steps=num_training_steps,
                              sched_stride=self.dp.world)
-        if self._resume is not None and self._resume.get("stage") == stage and self._resume.get("optimizer"):
+        if self._resuming(stage) and self._resume.get("optimizer"):
             opt.load_state_dict({k: ([t.to(self.device) for t in v] if isinstance(v, list) else v.to(self.device))
                                  for k, v in self._resume["optimizer"].items()})
             self.logger.info(f"Restored optimiser / scheduler state of stage {stage} "
@@ -198,10 +210,54 @@ class PreferenceGuidedTrainer:
         return self._train_loop(1, sc, opt, self.train_loader_stage1, self.val_loader_stage1, ContrastiveStep.prepare,
                                 micro, val, reducer, extra)
 
+    def train_caption(self) -> Dict[str, List[float]]:
+        """The caption (SFT) phase of Stage 2: the decoder's language-model loss on the chosen captions
+        (``steps.CaptionStep``; the reference's Stage 2 passes ``labels=`` on every forward, trainer.py:578-593, and
+        hands the loss out as ``generation_loss``).  Same loaders, trained segments, reducer, accumulation, NaN-skip and
+        validation as the DPO phase; its own optimiser and cosine schedule over Stage 2's epochs, at
+        ``mi355x.stage2.caption_learning_rate`` (null: Stage 2's rate).  Checkpoints carry ``_caption`` in their name."""
+        if self.train_loader_stage2 is None:
+            self.logger.warning("No stage 2 data loader provided, skipping the caption phase")
+            return {}
+        self.logger.info("Starting Stage 2 caption phase: language-model loss on the chosen captions")
+        self.current_stage, self._phase = 2, "caption"
+        try:
+            sc = dict(self.config.get_stage2_config())
+            lr = self.config.get("mi355x.stage2.caption_learning_rate")
+            if lr is not None:
+                sc["learning_rate"] = float(lr)
+            steps_per_epoch = len(self.train_loader_stage2) // sc.get("gradient_accumulation_steps", 1)
+            opt = self._setup_optimizer(2, steps_per_epoch * sc["num_epochs"], sc)
+            m = self.model
+            step = CaptionStep(m.store, m.ws, m.vision_encoder.tower, m.vision_encoder.head, m.caption_decoder.engine,
+                               self._dropout_plan(2), bool(self.config.get("mi355x.packed_rows", True)), self.recompute)
+            reducer = OverlappedTrunkReducer(self.dp, m.caption_decoder.engine.trunk,
+                                             group=int(self.config.get("mi355x.allreduce_layer_group", 4)))
+            extra = [s for s in opt.segments if s is not reducer.seg]
+
+            def micro(p, scale):
+                return step.loss_and_grads(p["image"], p["seq"], loss_scale=scale)
+
+            def val(p):
+                return step.loss_only(p["image"], p["seq"])
+
+            return self._train_loop(2, sc, opt, self.train_loader_stage2,
+                                    self.val_loader_stage2 or self.train_loader_stage2, CaptionStep.prepare, micro, val,
+                                    reducer, extra)
+        finally:
+            self._phase = "dpo"
+
     def train_stage2(self) -> Dict[str, List[float]]:
         if self.train_loader_stage2 is None:
             self.logger.warning("No stage 2 data loader provided, skipping stage 2")
             return {}
+        if self.objective == "caption":
+            return self.train_caption()
+        caption_metrics = None
+        if self.objective == "caption_then_dpo" and not self._resuming(2):   # (a DPO-phase checkpoint resumes DPO)
+            caption_metrics = self.train_caption()
+            # the two losses are not comparable: the DPO phase keeps its own best checkpoint and patience
+            self.best_val_loss, self.patience_counter = float("inf"), 0
         self.logger.info("Starting Stage 2: Preference Optimization")
         self.current_stage = 2
         sc = self.config.get_stage2_config()
@@ -209,12 +265,13 @@ class PreferenceGuidedTrainer:
         opt = self._setup_optimizer(2, steps_per_epoch * sc["num_epochs"])
         m = self.model
         reference_free = bool(self.config.get("mi355x.dpo.reference_free", True))
-        ref = None if reference_free else ReferencePolicy(m.store, m.ws)
+        # taken here, after the caption phase: under caption_then_dpo the frozen reference is the SFT model
+        ref = self.reference_policy = None if reference_free else ReferencePolicy(m.store, m.ws)
         step = DPOStep(m.store, m.ws, m.vision_encoder.tower, m.vision_encoder.head, m.caption_decoder.engine,
                        beta=self.beta, reference_free=reference_free,
                        label_smoothing=float(self.config.get("mi355x.dpo.label_smoothing", 0.0)), ref=ref,
                        dropout=self._dropout_plan(2), packed=bool(self.config.get("mi355x.packed_rows", True)),
-                       recompute=self.recompute)
+                       recompute=self.recompute, sft_alpha=float(self.config.get("mi355x.dpo.sft_alpha", 0.0)))
         reducer = OverlappedTrunkReducer(self.dp, m.caption_decoder.engine.trunk,
                                          group=int(self.config.get("mi355x.allreduce_layer_group", 4)))
         extra = [s for s in opt.segments if s is not reducer.seg]
@@ -225,16 +282,19 @@ class PreferenceGuidedTrainer:
         def val(p):
             return step.loss_only(p["image"], p["seq"])
 
-        return self._train_loop(2, sc, opt, self.train_loader_stage2,
-                                self.val_loader_stage2 or self.train_loader_stage2, DPOStep.prepare, micro, val, reducer,
-                                extra)
+        metrics = self._train_loop(2, sc, opt, self.train_loader_stage2,
+                                   self.val_loader_stage2 or self.train_loader_stage2, DPOStep.prepare, micro, val,
+                                   reducer, extra)
+        if caption_metrics is not None:
+            metrics["caption_metrics"] = caption_metrics
+        return metrics
 
     def _train_loop(self, stage, sc, opt, train_loader, val_loader, prepare, micro, val, reducer, extra):
         metrics: Dict[str, List[float]] = {"train_loss": [], "val_loss": [], "learning_rates": []}
         self._check_loader(train_loader, f"stage {stage} training loader")
         self._check_loader(val_loader, f"stage {stage} validation loader")
         first = 0
-        if self._resume is not None and self._resume.get("stage") == stage:
+        if self._resuming(stage):
             first = int(self._resume.get("epoch", -1)) + 1   # the reference restarts at epoch 0 (trainer.py:848)
             self._resume = None
         for epoch in range(first, sc["num_epochs"]):
@@ -317,13 +377,16 @@ class PreferenceGuidedTrainer:
               "val_loss": val_loss, "config": self.config.config,
               "mi355x_state": {"dropout_step": int(getattr(self, "_plan", DropoutPlan()).step),
                                "best_val_loss": min(self.best_val_loss, val_loss),
-                               "patience_counter": self.patience_counter}}
+                               "patience_counter": self.patience_counter,
+                               # the Stage-2 objective of the run and the phase of it that wrote this file
+                               "objective": self.objective, "phase": self._phase}}
         self.checkpoint_dir.mkdir(parents=True, exist_ok=True)
-        path = self.checkpoint_dir / f"checkpoint_stage{stage}_epoch{epoch}.pt"
+        tag = f"stage{stage}_caption" if (stage == 2 and self._phase == "caption") else f"stage{stage}"
+        path = self.checkpoint_dir / f"checkpoint_{tag}_epoch{epoch}.pt"
         torch.save(ck, path)
         if val_loss < self.best_val_loss:
             self.best_val_loss = val_loss
-            torch.save(ck, self.checkpoint_dir / f"best_model_stage{stage}.pt")
+            torch.save(ck, self.checkpoint_dir / f"best_model_{tag}.pt")
             self.logger.info(f"Saved best model with val_loss: {val_loss:.4f}")
         self.logger.info(f"Saved checkpoint: {path}")
 
@@ -335,11 +398,18 @@ class PreferenceGuidedTrainer:
         ck = torch.load(path, map_location="cpu", weights_only=False)
         self.model.load_state_dict(ck["model_state_dict"], strict=True)
         self.model.sync_bf16()
+        if ck.get("stage", 1) == 2 and checkpoint_objective(ck) != self.objective:
+            # a Stage-2 checkpoint of another objective (one without the key counts as "dpo"): its optimiser moments,
+            # schedule position and epoch belong to another loss - the weights only, training starts afresh
+            self._resume = None
+            self.logger.info(f"Loaded the weights of {path} (Stage-2 objective {checkpoint_objective(ck)!r}, this run "
+                             f"{self.objective!r}: optimiser, scheduler and epoch are not restored)")
+            return
         self.epoch, self.current_stage = ck.get("epoch", 0), ck.get("stage", 1)
         self.global_step = ck.get("global_step", 0)
         extra = ck.get("mi355x_state", {})
         self.best_val_loss = float(extra.get("best_val_loss", ck.get("val_loss", float("inf"))))
         self.patience_counter = int(extra.get("patience_counter", 0))
         self._resume = {"stage": self.current_stage, "epoch": self.epoch, "optimizer": ck.get("optimizer_state_dict"),
-                        "dropout_step": extra.get("dropout_step", 0)}
+                        "dropout_step": extra.get("dropout_step", 0), "phase": extra.get("phase", "dpo")}
         self.logger.info(f"Loaded checkpoint from {path}")

@@ -84,6 +84,9 @@ def main():
     ap.add_argument("--recompute", type=str, choices=["none", "mlp", "block"], default=None,
                     help="activation recompute of the GPT-2 trunks (overrides mi355x.recompute / "
                          "hardware.gradient_checkpointing)")
+    ap.add_argument("--objective", type=str, choices=["dpo", "caption", "caption_then_dpo"], default=None,
+                    help="what Stage 2 trains on (overrides mi355x.stage2.objective): the preference loss, the caption "
+                         "decoder's language-model loss, or the second after the first")
     args = ap.parse_args()
 
     logging.basicConfig(level=getattr(logging, args.log_level), format="%(asctime)s %(name)s %(levelname)s %(message)s")
@@ -93,6 +96,8 @@ def main():
         cfg.set("paths.output_dir", args.output_dir)
     if args.recompute is not None:
         cfg.set("mi355x.recompute", args.recompute)
+    if args.objective is not None:
+        cfg.set("mi355x.stage2.objective", args.objective)
     seed = int(cfg.get("training.seed", 42))
     set_random_seeds(seed)
     dp = DataParallel.init_from_env()
