@@ -405,6 +405,50 @@ int pgca_row_scale(const float* dseq, const int32_t* seq_of_row, const int32_t* 
 int pgca_token_nll(const float* tok_lp, const int32_t* seq_of_row, int32_t seq_limit, int32_t nrows, float grad_scale,
                    int32_t accumulate, float* loss, float* row_coef, float* metrics, void* stream);
 
+/* ------------------------------------------------------------------ preference-pair mining (Stage-2 data from the model) */
+/* The four steps between the ids that best-of-N sampling returns and a finished Stage-2 batch (reference
+ * data/loader.py:416-451, UltraFeedbackDataset._process_scored_captions, applied to the model's own captions).  One wave
+ * per candidate row or per image, no atomics, fixed-order sums: two launches on one input are bitwise equal.  Every
+ * output is written in full.
+ *
+ * Generated ids -> training rows and scorer rows.  cand int64 [R, ld_cand] in the DECODER's vocabulary (base_vocab
+ * ordinary ids, then [PAD] [BOS] [EOS]), lengths int64 [R] = generated tokens with [EOS]; len_r = min(lengths[r],
+ * ld_cand, S) (a negative length counts as 0).
+ *   dec_ids / dec_mask int64 [R, S]: cand[r, t] / 1 for t < len_r, else dec_pad / 0;
+ *   text_ids int64 / text_mask int32 [R, S]: the tokens with 0 <= id < base_vocab, in order, compacted to the left, then
+ *     text_pad / 0 - the decoder's special ids never reach the text tower, whose table ends at base_vocab + 2;
+ *   text_len int32 [R] = kept tokens; out_len int32 [R] = len_r.
+ * A row with an id outside [0, dec_vocab) in its first len_r columns is unusable: text_len = -1, out_len = 0, both rows
+ * all pad with mask 0. */
+int pgca_candidate_rows(const int64_t* cand, int32_t ld_cand, const int64_t* lengths, int32_t R, int32_t S,
+                        int32_t base_vocab, int32_t dec_vocab, int64_t dec_pad, int64_t text_pad, int64_t* dec_ids,
+                        int64_t* dec_mask, int64_t* text_ids, int32_t* text_mask, int32_t* text_len, int32_t* out_len,
+                        void* stream);
+/* score[b*n + j] = <img_b, txt_(bn+j)> / (max(|img_b|, 1e-12) * max(|txt_(bn+j)|, 1e-12)): F.normalize (model.py:828-829)
+ * of both sides, then the dot product, in f32.  img f32 [B, P], txt f32 [B*n, P] (un-normalised), any P >= 1. */
+int pgca_group_cosine(const float* img, const float* txt, int32_t B, int32_t n, int32_t P, float* score, void* stream);
+/* The pairing rule, one wave per image, 1 <= n <= 64.  score f32 [B, n]; dec_ids [B*n, S] / out_len [B*n] as written by
+ * pgca_candidate_rows; ok (optional) uint8 [B, n].  Candidate j is LEFT OUT when its score is not finite, ok is 0,
+ * out_len < min_tokens, or an earlier candidate i < j of the image has the same out_len and the same ids.  The rest are
+ * ranked by score descending, equal scores by ascending j (Python's stable sort(reverse=True), loader.py:435):
+ * rank int32 [B, n], -1 when left out.  rule 0 ("adjacent", the reference's): for k = 0 .. kept-2, d = s[rank k] -
+ * s[rank k+1] in f32, a pair (winner, loser, d) iff d >= threshold, in k order.  rule 1 ("best_worst"): at most one
+ * pair, first rank against last, same test.  pair_win / pair_lose int32 and pair_margin f32 [B, n] hold candidate
+ * indices within the image (unused slots: -1, -1, 0); pair_count int32 [B]. */
+int pgca_mine_pairs(const float* score, const int64_t* dec_ids, const int32_t* out_len, const uint8_t* ok, int32_t B,
+                    int32_t n, int32_t S, int32_t min_tokens, int32_t rule, float threshold, int32_t* rank,
+                    int32_t* pair_win, int32_t* pair_lose, float* pair_margin, int32_t* pair_count, void* stream);
+/* Batch assembly: pair p of image b lands at row sum(pair_count[0 .. b)) + p (images ascending: the reference's
+ * `extend` order); every workgroup sums the counts before its image itself.  For the first n_pairs rows
+ * preferred_* / rejected_* int64 [cap, S] are the winner's / loser's dec_ids and dec_mask rows, pair_image int32 [cap]
+ * = b, preference_score f32 [cap] = the margin (loader.py:448); n_pairs int32 [1].  Rows n_pairs .. cap-1: dec_pad,
+ * mask 0, pair_image -1, score 0.  cap >= max(1, B * (n - 1)). */
+int pgca_pair_rows(const int32_t* pair_win, const int32_t* pair_lose, const float* pair_margin,
+                   const int32_t* pair_count, const int64_t* dec_ids, const int64_t* dec_mask, int32_t B, int32_t n,
+                   int32_t S, int32_t cap, int64_t dec_pad, int64_t* preferred_ids, int64_t* preferred_mask,
+                   int64_t* rejected_ids, int64_t* rejected_mask, int32_t* pair_image, float* preference_score,
+                   int32_t* n_pairs, void* stream);
+
 /* ------------------------------------------------------------------ pooling / normalise (Stage 1) */
 /* pooled[b] = sum_s feats[b,s]*mask[b,s] / max(sum_s mask, 1)  (model.py:449-456); feats f32.
  * With cu_seqlens (int32 [B+1]) feats / dfeats are packed: position (b, s) is row cu[b] + s, s < cu[b+1]-cu[b]. */

@@ -17,9 +17,16 @@ MI355X_DEFAULTS = {
     # reference_free True = the reference trainer's 2-forward loss; sft_alpha > 0 adds sft_alpha * NLL(chosen) to the loss
     "dpo": {"reference_free": True, "label_smoothing": 0.0, "sft_alpha": 0.0},
     # what Stage 2 trains on: "dpo" (as the reference), "caption" (the LM loss of steps.CaptionStep on the chosen captions)
-    # or "caption_then_dpo" (caption phase, then DPO whose frozen reference policy is the captioner just trained);
+    # or "caption_then_dpo" (caption phase, then DPO whose frozen reference policy is the captioner just trained), or
+    # "mine_then_dpo" (DPO on pairs mined from the model's own captions: the "mining" section below);
     # caption_learning_rate: the caption phase's rate (null = training.stage2.learning_rate)
     "stage2": {"objective": "dpo", "caption_learning_rate": None},
+    # mine_then_dpo: the keywords of mining.PreferenceMiner (num_candidates <= 64; rule adjacent | best_worst; threshold
+    # is the reference's preference_threshold on the score difference; scorer alignment | logprob) and the seed of the
+    # sampling generator (null = training.seed)
+    "mining": {"num_candidates": 4, "rule": "adjacent", "threshold": 0.0, "scorer": "alignment", "max_length": 50,
+               "min_tokens": 2, "temperature": 1.0, "top_p": 0.9, "top_k": 0, "repetition_penalty": 1.1,
+               "no_repeat_ngram_size": 0, "decode_rows": 64, "seed": None},
     "stage1": {"global_negatives": False},                      # False = local negatives, as the reference
     "allreduce_bucket_elems": 64 * 1024 * 1024,
     "allreduce_layer_group": 4,
@@ -59,7 +66,7 @@ def select_recompute(config) -> str:
     return mode
 
 
-STAGE2_OBJECTIVES = ("dpo", "caption", "caption_then_dpo")
+STAGE2_OBJECTIVES = ("dpo", "caption", "caption_then_dpo", "mine_then_dpo")
 
 
 def select_objective(config) -> str:

@@ -396,6 +396,35 @@ def token_nll(tok_lp, seq_of_row, seq_limit, nrows, grad_scale, accumulate, loss
           metrics)
 
 
+# --------------------------------------------------------------------------- preference-pair mining
+MINE_RULES = {"adjacent": 0, "best_worst": 1}
+
+
+def candidate_rows(cand, lengths, R, S, base_vocab, dec_vocab, dec_pad, text_pad, dec_ids, dec_mask, text_ids, text_mask,
+                   text_len, out_len):
+    """``cand`` int64 [R, ld] rows of generated decoder ids (row stride = ``cand.stride(0)``) -> decoder rows and
+    text-tower rows of width ``S``; see pgca_hip.h."""
+    _call("pgca_candidate_rows", cand, cand.stride(0), lengths, R, S, base_vocab, dec_vocab, dec_pad, text_pad, dec_ids,
+          dec_mask, text_ids, text_mask, text_len, out_len)
+
+
+def group_cosine(img, txt, B, n, P, score):
+    _call("pgca_group_cosine", img, txt, B, n, P, score)
+
+
+def mine_pairs(score, dec_ids, out_len, ok, B, n, S, min_tokens, rule, threshold, rank, pair_win, pair_lose, pair_margin,
+               pair_count):
+    """``rule``: "adjacent" (the reference's) or "best_worst"; ``ok``: optional uint8 / bool [B, n]."""
+    _call("pgca_mine_pairs", score, dec_ids, out_len, ok, B, n, S, min_tokens, MINE_RULES[rule], threshold, rank,
+          pair_win, pair_lose, pair_margin, pair_count)
+
+
+def pair_rows(pair_win, pair_lose, pair_margin, pair_count, dec_ids, dec_mask, B, n, S, cap, dec_pad, preferred_ids,
+              preferred_mask, rejected_ids, rejected_mask, pair_image, preference_score, n_pairs):
+    _call("pgca_pair_rows", pair_win, pair_lose, pair_margin, pair_count, dec_ids, dec_mask, B, n, S, cap, dec_pad,
+          preferred_ids, preferred_mask, rejected_ids, rejected_mask, pair_image, preference_score, n_pairs)
+
+
 def masked_mean_fwd(feats, mask, B, S, H, pooled, cu=None):
     _call("pgca_masked_mean_fwd", feats, mask, B, S, H, pooled, cu)
 

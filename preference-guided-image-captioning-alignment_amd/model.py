@@ -662,13 +662,16 @@ class PreferenceGuidedCaptioningModel:
                             temperature: float = 1.0, top_p: float = 0.9, top_k: int = 0,
                             repetition_penalty: float = 1.1, generator: Optional[torch.Generator] = None,
                             use_cache: bool = True, no_repeat_ngram_size: int = 0, min_length: int = 0,
-                            suppress_tokens: Optional[List[int]] = None):
+                            suppress_tokens: Optional[List[int]] = None,
+                            image_embeddings: Optional[torch.Tensor] = None):
         """Best-of-N sampling, the step that turns a Stage-1 model into Stage-2 preference data: ``num_candidates``
         sampled captions per image with the model's own log-probability of each.  Returns ``(ids [B, n, L] int64,
         logp [B, n] f32, lengths [B, n] int64)``: ``logp`` sums the log-softmax of the raw logits over the generated
         tokens, [EOS] included and [PAD] excluded; ``lengths`` counts the same tokens.  Device-side selection;
         ``use_cache``, ``no_repeat_ngram_size``, ``min_length`` and ``suppress_tokens`` as in ``generate`` (they steer
-        the draw; ``logp`` stays the log-softmax of the raw logits)."""
+        the draw; ``logp`` stays the log-softmax of the raw logits).  ``image_embeddings`` [B, P]: the vision encoder's
+        output for ``images`` when the caller already has it (``mining.PreferenceMiner`` scores with the same vector);
+        the ViT is then not run again."""
         n = int(num_candidates)
         if n < 1:
             raise ValueError(f"num_candidates={num_candidates}: expected at least 1")
@@ -680,7 +683,7 @@ class PreferenceGuidedCaptioningModel:
         try:
             dec = self.caption_decoder
             base = self.arch.gpt.base_vocab
-            emb = self.vision_encoder(images)["embeddings"]
+            emb = self.vision_encoder(images)["embeddings"] if image_embeddings is None else image_embeddings
             B = emb.shape[0]
             pv = dec.engine.prefix_embedding(emb.to(self.device, F32).contiguous()).repeat_interleave(n, dim=0)
             bans = dec._ban_schedule(L, base + 2, min_length, None, suppress_tokens)
@@ -691,6 +694,12 @@ class PreferenceGuidedCaptioningModel:
             return ids_buf[:, :cols].reshape(B, n, -1).contiguous(), logp.view(B, n), lengths.view(B, n)
         finally:
             self.train(was)
+
+    def mine_preferences(self, images: torch.Tensor, generator: Optional[torch.Generator] = None, **kw) -> Dict[str, Any]:
+        """Stage-2 preference pairs from this model's own captions for ``images``: ``mining.PreferenceMiner(self,
+        **kw).mine(images, generator)`` - a batch dict ``steps.DPOStep.prepare`` takes as it is."""
+        from .mining import PreferenceMiner
+        return PreferenceMiner(self, **kw).mine(images, generator=generator)
 
     def generate_captions(self, images: torch.Tensor, max_length: int = 50, num_beams: int = 4, temperature: float = 1.0,
                           do_sample: bool = True, top_p: float = 0.9, **kwargs) -> List[str]:

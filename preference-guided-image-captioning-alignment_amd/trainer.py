@@ -36,10 +36,11 @@ from typing import Any, Dict, Iterable, List, Optional
 
 import torch
 
-from .config import checkpoint_objective, select_objective, select_recompute
+from .config import MI355X_DEFAULTS, checkpoint_objective, select_objective, select_recompute
 from .dist import DataParallel, OverlappedTrunkReducer
 from .engine import DropoutPlan
 from .input import BatchPrefetcher
+from .mining import MinedPreferenceData, PreferenceMiner
 from .model import PreferenceGuidedCaptioningModel
 from .steps import CaptionStep, ContrastiveStep, DPOStep, FusedOptimizer, ReferencePolicy
 
@@ -62,7 +63,8 @@ class PreferenceGuidedTrainer:
         self.beta = float(config.get("training.stage2.dpo_beta", 0.1))
         # mi355x.recompute, else the reference's hardware.gradient_checkpointing (config.select_recompute)
         self.recompute = select_recompute(config)
-        # what Stage 2 trains on: mi355x.stage2.objective = dpo | caption | caption_then_dpo (config.select_objective)
+        # what Stage 2 trains on: mi355x.stage2.objective = dpo | caption | caption_then_dpo | mine_then_dpo
+        # (config.select_objective)
         self.objective = select_objective(config)
         self._phase = "dpo"                              # the phase of Stage 2 that is running: "caption" or "dpo"
         self.reference_policy: Optional[ReferencePolicy] = None   # the frozen pi_ref of the last 4-forward DPO phase
@@ -247,8 +249,57 @@ class PreferenceGuidedTrainer:
         finally:
             self._phase = "dpo"
 
+    # ------------------------------------------------------------------ mine_then_dpo: the model makes its own pairs
+    def _mine(self, miner: PreferenceMiner, loader, generator, what: str) -> MinedPreferenceData:
+        """One mining pass over ``loader`` (only ``image`` is read); logs the yield on rank 0."""
+        data = MinedPreferenceData()
+        for batch in loader:
+            data.add(miner.mine(batch["image"], generator=generator))
+        st = data.stats
+        self._log_metrics({"mined": what, "stage": 2, "mined_images": st["images"], "mined_pairs": st["pairs"],
+                           "pairs_per_image": st["pairs"] / max(1, st["images"]),
+                           # candidates the pairing never saw: duplicates of an earlier one, shorter than min_tokens, unscorable
+                           "candidates_left_out": st["left_out"] / max(1, st["candidates"])})
+        return data
+
+    def _even_batches(self, data: MinedPreferenceData, batch_size: int, drop_last: bool) -> int:
+        """Batches every rank can serve: each rank mined its own shard, all of them cut to the smallest count."""
+        n = len(data) // batch_size if drop_last else -(-len(data) // batch_size)
+        return int(-self.dp.all_reduce_max_scalar(-float(n), self.device))
+
+    def _mined_loaders(self, sc: Dict[str, Any]):
+        """Stage-2 loaders of pairs mined with the current weights (``mi355x.mining``) from the images of the Stage-2
+        loaders, or of Stage 1's where there are none.  A validation loader that already carries pairs is kept."""
+        mc = {**MI355X_DEFAULTS["mining"], **(self.config.get("mi355x.mining") or {})}
+        seed = mc.pop("seed")
+        seed = int(self.config.get("training.seed", 42)) if seed is None else int(seed)
+        generator = torch.Generator(device=self.device).manual_seed(seed * 1000 + self.dp.rank)
+        miner = PreferenceMiner(self.model, **mc)
+        bs = int(sc["batch_size"])
+        source = self.train_loader_stage2 if self.train_loader_stage2 is not None else self.train_loader_stage1
+        self.logger.info(f"Mining preference pairs: {mc['num_candidates']} captions per image, scorer "
+                         f"{mc['scorer'] if isinstance(mc['scorer'], str) else 'callable'}, rule {mc['rule']}, "
+                         f"threshold {mc['threshold']}")
+        train = self._mine(miner, source, generator, "train")
+        n_train = self._even_batches(train, bs, True)
+        if n_train == 0:
+            raise RuntimeError(f"mine_then_dpo: mining gave {len(train)} pairs on rank {self.dp.rank} and not one batch of "
+                               f"{bs} on every rank; lower mi355x.mining.threshold (now {mc['threshold']}) or raise "
+                               "mi355x.mining.num_candidates")
+        train_loader = train.loader(bs, shuffle=True, seed=seed, drop_last=True, max_batches=n_train)
+        val_source = self.val_loader_stage2 if self.val_loader_stage2 is not None else self.val_loader_stage1
+        if val_source is not None and "preferred_ids" in next(iter(val_source)):
+            return train_loader, val_source
+        val = train if val_source is None else self._mine(miner, val_source, generator, "validation")
+        n_val = self._even_batches(val, bs, False)
+        if n_val == 0:
+            self.logger.warning("No validation pairs were mined on some rank: validating on the mined training pairs")
+            val, n_val = train, n_train
+        return train_loader, val.loader(bs, shuffle=False, drop_last=False, max_batches=n_val)
+
     def train_stage2(self) -> Dict[str, List[float]]:
-        if self.train_loader_stage2 is None:
+        mining = self.objective == "mine_then_dpo"
+        if self.train_loader_stage2 is None and not (mining and self.train_loader_stage1 is not None):
             self.logger.warning("No stage 2 data loader provided, skipping stage 2")
             return {}
         if self.objective == "caption":
@@ -261,7 +312,10 @@ class PreferenceGuidedTrainer:
         self.logger.info("Starting Stage 2: Preference Optimization")
         self.current_stage = 2
         sc = self.config.get_stage2_config()
-        steps_per_epoch = len(self.train_loader_stage2) // sc.get("gradient_accumulation_steps", 1)
+        train_loader, val_loader = self.train_loader_stage2, self.val_loader_stage2 or self.train_loader_stage2
+        if mining:      # before the reference policy is frozen and the optimiser sized; a resumed run mines again
+            train_loader, val_loader = self._mined_loaders(sc)
+        steps_per_epoch = len(train_loader) // sc.get("gradient_accumulation_steps", 1)
         opt = self._setup_optimizer(2, steps_per_epoch * sc["num_epochs"])
         m = self.model
         reference_free = bool(self.config.get("mi355x.dpo.reference_free", True))
@@ -282,9 +336,7 @@ class PreferenceGuidedTrainer:
         def val(p):
             return step.loss_only(p["image"], p["seq"])
 
-        metrics = self._train_loop(2, sc, opt, self.train_loader_stage2,
-                                   self.val_loader_stage2 or self.train_loader_stage2, DPOStep.prepare, micro, val,
-                                   reducer, extra)
+        metrics = self._train_loop(2, sc, opt, train_loader, val_loader, DPOStep.prepare, micro, val, reducer, extra)
         if caption_metrics is not None:
             metrics["caption_metrics"] = caption_metrics
         return metrics

@@ -18,7 +18,7 @@ from torch.utils.data import DataLoader, Dataset
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from pgca_amd.config import Config  # noqa: E402
+from pgca_amd.config import Config, select_objective  # noqa: E402
 from pgca_amd.dist import DataParallel  # noqa: E402
 
 
@@ -84,9 +84,11 @@ def main():
     ap.add_argument("--recompute", type=str, choices=["none", "mlp", "block"], default=None,
                     help="activation recompute of the GPT-2 trunks (overrides mi355x.recompute / "
                          "hardware.gradient_checkpointing)")
-    ap.add_argument("--objective", type=str, choices=["dpo", "caption", "caption_then_dpo"], default=None,
+    ap.add_argument("--objective", type=str, choices=["dpo", "caption", "caption_then_dpo", "mine_then_dpo"],
+                    default=None,
                     help="what Stage 2 trains on (overrides mi355x.stage2.objective): the preference loss, the caption "
-                         "decoder's language-model loss, or the second after the first")
+                         "decoder's language-model loss, the second after the first, or the preference loss on pairs "
+                         "mined from the model's own captions (only the images of the Stage-2 data are read)")
     args = ap.parse_args()
 
     logging.basicConfig(level=getattr(logging, args.log_level), format="%(asctime)s %(name)s %(levelname)s %(message)s")
@@ -127,7 +129,9 @@ def main():
                 DataLoader(va, batch_size=bs, shuffle=False, drop_last=True))
 
     tl1, vl1 = loaders(False, int(cfg.get("training.stage1.batch_size", 8)), seed)
-    tl2, vl2 = loaders(True, int(cfg.get("training.stage2.batch_size", 8)), seed + 7)
+    # mine_then_dpo makes its own pairs: its Stage-2 loaders only have to carry images
+    mined = select_objective(cfg) == "mine_then_dpo"
+    tl2, vl2 = loaders(not mined, int(cfg.get("training.stage2.batch_size", 8)), seed + 7)
     trainer = PreferenceGuidedTrainer(model, cfg, tl1, vl1, tl2, vl2)
     if args.resume:
         trainer.load_checkpoint(args.resume)
