@@ -449,6 +449,50 @@ int pgca_pair_rows(const int32_t* pair_win, const int32_t* pair_lose, const floa
                    int64_t* rejected_ids, int64_t* rejected_mask, int32_t* pair_image, float* preference_score,
                    int32_t* n_pairs, void* stream);
 
+/* ------------------------------------------------------------------ caption metrics over token ids */
+/* The reference's evaluation formulas (evaluation/metrics.py) with a base-vocabulary token id in the place of a word.
+ * Inputs are STRIPPED rows: ids int64 [.., S] as pgca_candidate_rows writes text_ids (0 <= id < base_vocab in the first
+ * len columns), len int32 (a reference with len -1 is ABSENT, with len 0 present and empty; a len above S counts as S,
+ * a negative prediction length as 0).  One 64-lane workgroup per image, no atomics, loops bounded by S, K and a 32-step
+ * search, fixed-order sums: two launches on one input are bitwise equal.  Limits, checked before any launch:
+ * 1 <= S <= PGCA_EVAL_MAX_S, 1 <= K <= PGCA_EVAL_MAX_K, 1 <= base_vocab <= PGCA_EVAL_MAX_VOCAB, images (rows, groups)
+ * 1 .. PGCA_EVAL_MAX_IMAGES - 1, no null pointer.
+ *
+ * An n-gram of order n <= 4 is the int64 KEY of its ids at 16 bits each, the first id most significant; the orders are
+ * kept apart, so keys of different orders never meet.  base_vocab <= 65535 leaves the field 0xffff unused and -1 free
+ * as "no n-gram here".  A key whose leading id is >= 32768 is negative: tables are sorted in SIGNED order (torch.sort on
+ * int64) and searched in it. */
+#define PGCA_EVAL_MAX_S 128
+#define PGCA_EVAL_MAX_K 8
+#define PGCA_EVAL_MAX_VOCAB 65535
+#define PGCA_EVAL_MAX_IMAGES 16777216
+/* keys_out int64 [G, K, S]: the key of the n-gram of `order` starting at each column, -1 where there is none.
+ * distinct_per_group != 0: a key is written only at its first occurrence in the group (all K rows of image g, row
+ * major) and -1 at the later ones - the reference's once-per-image document frequency (metrics.py:489-501). */
+int pgca_ngram_keys(const int64_t* ids, const int32_t* len, int32_t G, int32_t K, int32_t S, int32_t order,
+                    int32_t base_vocab, int32_t distinct_per_group, int64_t* keys_out, void* stream);
+/* _compute_cider (metrics.py:463-572) per image, in float64.  table_keys / table_df int64 [table_len]: per order the
+ * sorted distinct keys of the corpus and their document frequencies, order n in [table_off[n-1], table_off[n])
+ * (table_off int64 [5], on the device; offsets are clamped to table_len).  Per order 1..4: prediction counts pc,
+ * reference counts rc = sum over present references of count / K_present, idf = log(n_docs / (df + 1e-8)) with df = 1
+ * for a key the table lacks; num = sum pc idf rc idf, pn = sum (pc idf)^2, rn = sum (rc idf)^2 over the n-grams of
+ * either side; sim = num / sqrt(pn rn) when pn > 0 and rn > 0, else 0.  score = mean of the four sims times
+ * exp(-(pred_len - mean ref_len)^2 / (2 sigma^2)) (0 when the mean is 0).  score_out FLOAT64 [N] (the x10 and the corpus
+ * mean are the caller's); flag_out int32 [N] = 1 and score 0 for an image with no present reference, else 0. */
+int pgca_cider_rows(const int64_t* pred_ids, const int32_t* pred_len, const int64_t* ref_ids, const int32_t* ref_len,
+                    int32_t N, int32_t K, int32_t S, int32_t base_vocab, const int64_t* table_keys,
+                    const int64_t* table_df, const int64_t* table_off, int64_t table_len, int32_t n_docs, float sigma,
+                    void* score_out, int32_t* flag_out, void* stream);
+/* stats_out int64 [N, 10]: clipped matches of orders 1..4 (sum over the distinct n-grams of the prediction of
+ * min(prediction count, max over references of reference count)), possible matches max(0, pred_len - n + 1) of orders
+ * 1..4, pred_len, and the MINIMUM length over the present references (0 when none is). */
+int pgca_bleu_stats(const int64_t* pred_ids, const int32_t* pred_len, const int64_t* ref_ids, const int32_t* ref_len,
+                    int32_t N, int32_t K, int32_t S, int32_t base_vocab, int64_t* stats_out, void* stream);
+/* out int32 [R, 2] = |set(a_r) & set(b_r)|, |set(a_r) | set(b_r)| over the ids of the first len columns (the integers
+ * of the reference's Jaccard similarity, metrics.py:638-661; the caller divides). */
+int pgca_token_overlap(const int64_t* a_ids, const int32_t* a_len, const int64_t* b_ids, const int32_t* b_len,
+                       int32_t R, int32_t S, int32_t* out, void* stream);
+
 /* ------------------------------------------------------------------ pooling / normalise (Stage 1) */
 /* pooled[b] = sum_s feats[b,s]*mask[b,s] / max(sum_s mask, 1)  (model.py:449-456); feats f32.
  * With cu_seqlens (int32 [B+1]) feats / dfeats are packed: position (b, s) is row cu[b] + s, s < cu[b+1]-cu[b]. */

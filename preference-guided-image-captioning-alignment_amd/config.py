@@ -27,6 +27,10 @@ MI355X_DEFAULTS = {
     "mining": {"num_candidates": 4, "rule": "adjacent", "threshold": 0.0, "scorer": "alignment", "max_length": 50,
                "min_tokens": 2, "temperature": 1.0, "top_p": 0.9, "top_k": 0, "repetition_penalty": 1.1,
                "no_repeat_ngram_size": 0, "decode_rows": 64, "seed": None},
+    # caption metrics on the Stage-2 validation loader (evaluation.CaptionEvaluator) after every every_epochs-th epoch's
+    # validation; 0 = never (the trainer then does, logs and returns what it did without this section); max_batches:
+    # evaluate only the first so many batches (null = all)
+    "evaluation": {"every_epochs": 0, "max_batches": None},
     "stage1": {"global_negatives": False},                      # False = local negatives, as the reference
     "allreduce_bucket_elems": 64 * 1024 * 1024,
     "allreduce_layer_group": 4,
@@ -84,6 +88,25 @@ def select_objective(config) -> str:
 def checkpoint_objective(ck: dict) -> str:
     """The Stage-2 objective a checkpoint dict was written under; one from before the key existed counts as ``"dpo"``."""
     return ck.get("mi355x_state", {}).get("objective", "dpo")
+
+
+def select_evaluation(config) -> Optional[Dict[str, Any]]:
+    """``mi355x.evaluation`` of a ``Config`` or a plain nested dict over its defaults, or ``None`` when
+    ``every_epochs`` is 0 (the default): caption evaluation during training is off."""
+    cur = getattr(config, "config", config)
+    for key in ("mi355x", "evaluation"):
+        cur = cur.get(key) if isinstance(cur, dict) else None
+    unknown = sorted(set(cur or {}) - set(MI355X_DEFAULTS["evaluation"]))
+    if unknown:
+        raise ValueError(f"mi355x.evaluation: unknown keys {unknown}; known: {sorted(MI355X_DEFAULTS['evaluation'])}")
+    section = {**MI355X_DEFAULTS["evaluation"], **(cur or {})}
+    every = int(section["every_epochs"] or 0)
+    if every < 0:
+        raise ValueError(f"mi355x.evaluation.every_epochs must be >= 0, got {section['every_epochs']!r}")
+    if every == 0:
+        return None
+    mb = section["max_batches"]
+    return {"every_epochs": every, "max_batches": None if mb is None else int(mb)}
 
 
 GENERATE_KEYS = {"max_length": int, "num_beams": int, "temperature": float, "do_sample": bool, "top_p": float,

@@ -425,6 +425,30 @@ def pair_rows(pair_win, pair_lose, pair_margin, pair_count, dec_ids, dec_mask, B
           preferred_ids, preferred_mask, rejected_ids, rejected_mask, pair_image, preference_score, n_pairs)
 
 
+# --------------------------------------------------------------------------- caption metrics over token ids
+EVAL_MAX_S, EVAL_MAX_K, EVAL_MAX_VOCAB = _K["PGCA_EVAL_MAX_S"], _K["PGCA_EVAL_MAX_K"], _K["PGCA_EVAL_MAX_VOCAB"]
+
+
+def ngram_keys(ids, lengths, G, K, S, order, base_vocab, distinct_per_group, keys_out):
+    """Stripped rows ``ids`` int64 [G, K, S] / ``lengths`` int32 [G, K] -> int64 keys [G, K, S] (-1: no n-gram)."""
+    _call("pgca_ngram_keys", ids, lengths, G, K, S, order, base_vocab, int(bool(distinct_per_group)), keys_out)
+
+
+def cider_rows(pred_ids, pred_len, ref_ids, ref_len, N, K, S, base_vocab, table_keys, table_df, table_off, n_docs,
+               sigma, score_out, flag_out):
+    """``score_out`` float64 [N], ``flag_out`` int32 [N]; ``table_off`` int64 [5] on the device; see pgca_hip.h."""
+    _call("pgca_cider_rows", pred_ids, pred_len, ref_ids, ref_len, N, K, S, base_vocab, table_keys, table_df, table_off,
+          table_keys.numel(), n_docs, sigma, score_out, flag_out)
+
+
+def bleu_stats(pred_ids, pred_len, ref_ids, ref_len, N, K, S, base_vocab, stats_out):
+    _call("pgca_bleu_stats", pred_ids, pred_len, ref_ids, ref_len, N, K, S, base_vocab, stats_out)
+
+
+def token_overlap(a_ids, a_len, b_ids, b_len, R, S, out):
+    _call("pgca_token_overlap", a_ids, a_len, b_ids, b_len, R, S, out)
+
+
 def masked_mean_fwd(feats, mask, B, S, H, pooled, cu=None):
     _call("pgca_masked_mean_fwd", feats, mask, B, S, H, pooled, cu)
 

@@ -36,9 +36,10 @@ from typing import Any, Dict, Iterable, List, Optional
 
 import torch
 
-from .config import MI355X_DEFAULTS, checkpoint_objective, select_objective, select_recompute
+from .config import MI355X_DEFAULTS, checkpoint_objective, select_evaluation, select_objective, select_recompute
 from .dist import DataParallel, OverlappedTrunkReducer
 from .engine import DropoutPlan
+from .evaluation import CaptionEvaluator, FirstBatches
 from .input import BatchPrefetcher
 from .mining import MinedPreferenceData, PreferenceMiner
 from .model import PreferenceGuidedCaptioningModel
@@ -66,6 +67,9 @@ class PreferenceGuidedTrainer:
         # what Stage 2 trains on: mi355x.stage2.objective = dpo | caption | caption_then_dpo | mine_then_dpo
         # (config.select_objective)
         self.objective = select_objective(config)
+        # mi355x.evaluation: caption metrics after Stage-2 validation; None = off (config.select_evaluation)
+        self._eval_cfg = select_evaluation(config)
+        self._eval_corpora: Dict[int, Any] = {}          # id(loader) -> (loader, evaluator, batches, ReferenceCorpus)
         self._phase = "dpo"                              # the phase of Stage 2 that is running: "caption" or "dpo"
         self.reference_policy: Optional[ReferencePolicy] = None   # the frozen pi_ref of the last 4-forward DPO phase
         self.current_stage, self.global_step, self.epoch = 1, 0, 0
@@ -358,6 +362,8 @@ class PreferenceGuidedTrainer:
             metrics["train_loss"].append(train_loss)
             metrics["val_loss"].append(val_loss)
             metrics["learning_rates"].append(lr)
+            if stage == 2 and self._eval_cfg is not None and (epoch + 1) % self._eval_cfg["every_epochs"] == 0:
+                metrics.setdefault("eval", []).append(self._evaluate_captions(val_loader, epoch))
             self._log_metrics({"epoch": epoch, "stage": stage, "train_loss": train_loss, "val_loss": val_loss,
                                "learning_rate": lr, "epoch_seconds": time.time() - t0})
             # every rank runs the same bookkeeping on the same (rank-reduced) val_loss, so all of them leave the loop
@@ -373,6 +379,20 @@ class PreferenceGuidedTrainer:
                 break
         self.logger.info(f"Completed Stage {stage} training")
         return metrics
+
+    def _evaluate_captions(self, loader, epoch: int) -> Dict[str, float]:
+        """Caption metrics of the current weights on the Stage-2 validation loader (``mi355x.evaluation``).  The
+        references do not change between epochs: their corpus is built once per loader.  Under data parallelism every
+        rank evaluates its own copy of the loader and rank 0 logs; the evaluation is not sharded."""
+        cached = self._eval_corpora.get(id(loader))
+        if cached is None:
+            evaluator = CaptionEvaluator(self.model, config=self.config, measure_latency=True)
+            batches = FirstBatches(loader, self._eval_cfg["max_batches"])
+            cached = self._eval_corpora[id(loader)] = (loader, evaluator, batches, evaluator.build_corpus(batches))
+        _, evaluator, batches, corpus = cached
+        result = evaluator.evaluate(batches, corpus=corpus)
+        self._log_metrics({"eval": "captions", "stage": 2, "epoch": epoch, **result})
+        return result
 
     def train(self) -> Dict[str, Any]:
         """Reference ``train`` (trainer.py:855-884): both stages, then the same result dict.  As in the reference
