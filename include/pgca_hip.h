@@ -454,7 +454,8 @@ int pgca_pair_rows(const int32_t* pair_win, const int32_t* pair_lose, const floa
  * Inputs are STRIPPED rows: ids int64 [.., S] as pgca_candidate_rows writes text_ids (0 <= id < base_vocab in the first
  * len columns), len int32 (a reference with len -1 is ABSENT, with len 0 present and empty; a len above S counts as S,
  * a negative prediction length as 0).  One 64-lane workgroup per image, no atomics, loops bounded by S, K and a 32-step
- * search, fixed-order sums: two launches on one input are bitwise equal.  Limits, checked before any launch:
+ * search, fixed-order sums: two launches on one input are bitwise equal.  Like BLEU and CIDEr here, ROUGE and METEOR over
+ * BPE ids are not comparable with their word-level namesakes.  Limits, checked before any launch:
  * 1 <= S <= PGCA_EVAL_MAX_S, 1 <= K <= PGCA_EVAL_MAX_K, 1 <= base_vocab <= PGCA_EVAL_MAX_VOCAB, images (rows, groups)
  * 1 .. PGCA_EVAL_MAX_IMAGES - 1, no null pointer.
  *
@@ -492,6 +493,22 @@ int pgca_bleu_stats(const int64_t* pred_ids, const int32_t* pred_len, const int6
  * of the reference's Jaccard similarity, metrics.py:638-661; the caller divides). */
 int pgca_token_overlap(const int64_t* a_ids, const int32_t* a_len, const int64_t* b_ids, const int32_t* b_len,
                        int32_t R, int32_t S, int32_t* out, void* stream);
+/* The integers of ROUGE-1 / ROUGE-2 / ROUGE-L (metrics.py:291-300) of the prediction against the FIRST PRESENT reference
+ * (the lowest k with ref_len[i, k] >= 0).  out int32 [N, 6] = overlap_1, overlap_2 (sum over the distinct n-grams of
+ * the reference of min(prediction count, reference count)), lcs (length of the longest common subsequence), pred_len,
+ * ref_len, k_used; an image with no present reference gets k_used = -1 and 0 in the other five.  The caller forms
+ * P = overlap_n / max(len - n + 1, 1), lcs / len and F = 2PR / (P + R).  The LCS is the bit-vector recurrence over the
+ * ballot of the prediction row (two 64-bit words for S <= 128): ref_len wave-uniform steps. */
+int pgca_rouge_stats(const int64_t* pred_ids, const int32_t* pred_len, const int64_t* ref_ids, const int32_t* ref_len,
+                     int32_t N, int32_t K, int32_t S, int32_t base_vocab, int32_t* out, void* stream);
+/* The integers of METEOR's exact-match stage (nltk meteor_score as HF `meteor` calls it, metrics.py:302-310) per
+ * reference.  out int32 [N, K, 2] = m, chunks; an absent reference gets -1, -1.  Matching: the prediction's positions
+ * from the last to the first, each to the highest still-unmatched reference position holding the same id; chunks = the
+ * matches (i, j) whose predecessor (i - 1, j - 1) is not a match.  The caller forms P = m / pred_len, R = m / ref_len,
+ * F = PR / (0.9 P + 0.1 R), score = (1 - 0.5 (chunks / m)^3) F and the maximum over the present references. */
+int pgca_meteor_stats(const int64_t* pred_ids, const int32_t* pred_len, const int64_t* ref_ids,
+                      const int32_t* ref_len, int32_t N, int32_t K, int32_t S, int32_t base_vocab, int32_t* out,
+                      void* stream);
 
 /* ------------------------------------------------------------------ pooling / normalise (Stage 1) */
 /* pooled[b] = sum_s feats[b,s]*mask[b,s] / max(sum_s mask, 1)  (model.py:449-456); feats f32.

@@ -3,10 +3,13 @@
 //   pgca_cider_rows     _compute_cider (metrics.py:463-572) per image, in float64
 //   pgca_bleu_stats     the ten integers of corpus BLEU per image
 //   pgca_token_overlap  |set(a) & set(b)| and |set(a) | set(b)| (_compute_text_similarity, metrics.py:638-661)
+//   pgca_rouge_stats    n-gram overlaps of orders 1 and 2 and the longest common subsequence, against the first reference
+//   pgca_meteor_stats   matches and chunks of METEOR's exact-match stage, per reference
 // One 64-lane workgroup per image (or row pair); the keys of the image sit in LDS and every lane scans them for its own
-// positions.  No atomics, nothing between workgroups, no waiting; every loop is bounded by S, K or the 32 steps of the
-// table search; every floating-point sum is lane-strided in ascending order and then the xor tree: two launches on one
-// input are bitwise equal.
+// positions.  The order-sensitive pair works on ballots instead: a whole row compared with one id is one 64-bit mask per
+// 64 columns, the same in every lane.  No atomics, nothing between workgroups, no waiting; every loop is bounded by S,
+// K or the 32 steps of the table search; every floating-point sum is lane-strided in ascending order and then the xor
+// tree: two launches on one input are bitwise equal.
 #include "common.h"
 
 namespace pgca {
@@ -242,6 +245,128 @@ token_overlap_kernel(const long long* __restrict__ a_ids, const int* __restrict_
   }
 }
 
+// the first len of 64 positions starting at column `from`, as a bit mask
+__device__ __forceinline__ unsigned long long live_mask(int len, int from) {
+  const int n = len - from;
+  return n <= 0 ? 0ull : (n >= 64 ? ~0ull : ((1ull << n) - 1ull));
+}
+
+__global__ void __launch_bounds__(64)
+rouge_stats_kernel(const long long* __restrict__ pred_ids, const int* __restrict__ pred_len,
+                   const long long* __restrict__ ref_ids, const int* __restrict__ ref_len, int K, int S,
+                   int* __restrict__ stats) {
+  __shared__ long long keys[2 * EVAL_MAX_S];  // the prediction's keys, then the reference's
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int* rlen = ref_len + (size_t)b * K;
+  int* out = stats + (size_t)b * 6;
+  int used = -1;  // the first present reference
+  for (int k = K - 1; k >= 0; --k) used = rlen[k] >= 0 ? k : used;
+  if (used < 0) {  // the whole workgroup leaves: no barrier was reached
+    if (lane < 6) out[lane] = lane == 5 ? -1 : 0;
+    return;
+  }
+  const long long* pred = pred_ids + (size_t)b * S;
+  const long long* ref = ref_ids + ((size_t)b * K + used) * S;
+  const int plen = clamp_len(pred_len[b], S), len = clamp_len(rlen[used], S);
+  // ROUGE-1 / ROUGE-2: every distinct n-gram of the reference, at its first position there
+  for (int n = 1; n <= 2; ++n) {
+    __syncthreads();
+    fill_keys(keys, pred, plen, S, n, lane);
+    fill_keys(keys + S, ref, len, S, n, lane);
+    __syncthreads();
+    int overlap = 0;
+    for (int p = lane; p < S; p += 64) {
+      const long long key = keys[S + p];
+      if (key == NO_KEY) continue;
+      bool first = true;
+      int pc = 0, rc = 0;
+      for (int t = 0; t < S; ++t) {
+        const bool m = keys[S + t] == key;
+        rc += m ? 1 : 0;
+        first &= !(m && t < p);
+        pc += keys[t] == key ? 1 : 0;
+      }
+      overlap += first ? (pc < rc ? pc : rc) : 0;
+    }
+    overlap = wave_sum(overlap);
+    if (lane == 0) out[n - 1] = overlap;
+  }
+  // ROUGE-L: bit t of word w is prediction column 64 w + t.  V starts all ones; per reference id with match vector M:
+  // U = V & M, V = (V + U) | (V & ~U), the add carrying from word 0 into word 1; the zero bits of V among the live
+  // columns count the longest common subsequence.  Every value below is the same in all lanes.
+  const long long a0 = lane < plen ? pred[lane] : 0, a1 = 64 + lane < plen ? pred[64 + lane] : 0;
+  const unsigned long long live0 = live_mask(plen, 0), live1 = live_mask(plen, 64);
+  unsigned long long v0 = ~0ull, v1 = ~0ull;
+  for (int j = 0; j < len; ++j) {
+    const long long id = ref[j];
+    const unsigned long long u0 = v0 & __ballot(a0 == id) & live0, u1 = v1 & __ballot(a1 == id) & live1;
+    const unsigned long long s0 = v0 + u0;
+    const unsigned long long s1 = v1 + u1 + (s0 < v0 ? 1ull : 0ull);
+    v0 = s0 | (v0 & ~u0);
+    v1 = s1 | (v1 & ~u1);
+  }
+  if (lane == 0) {
+    out[2] = __popcll(~v0 & live0) + __popcll(~v1 & live1);
+    out[3] = plen;
+    out[4] = len;
+    out[5] = used;
+  }
+}
+
+__global__ void __launch_bounds__(64)
+meteor_stats_kernel(const long long* __restrict__ pred_ids, const int* __restrict__ pred_len,
+                    const long long* __restrict__ ref_ids, const int* __restrict__ ref_len, int K, int S,
+                    int* __restrict__ stats) {
+  __shared__ long long pred[EVAL_MAX_S];
+  __shared__ int match[EVAL_MAX_S];  // the reference position matched to each prediction position, -1 for none
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int plen = clamp_len(pred_len[b], S);
+  for (int t = lane; t < S; t += 64) pred[t] = pred_ids[(size_t)b * S + t];
+  __syncthreads();
+  for (int k = 0; k < K; ++k) {
+    int* out = stats + ((size_t)b * K + k) * 2;
+    const int l = ref_len[(size_t)b * K + k];
+    if (l < 0) {  // the same in every lane: nobody waits below
+      if (lane < 2) out[lane] = -1;
+      continue;
+    }
+    const int len = clamp_len(l, S);
+    const long long* ref = ref_ids + ((size_t)b * K + k) * S;
+    // bit t of word w is reference column 64 w + t; free0 / free1 are the positions not yet matched
+    const long long r0 = lane < len ? ref[lane] : 0, r1 = 64 + lane < len ? ref[64 + lane] : 0;
+    unsigned long long free0 = live_mask(len, 0), free1 = live_mask(len, 64);
+    for (int i = plen - 1; i >= 0; --i) {
+      const long long id = pred[i];
+      const unsigned long long m0 = __ballot(r0 == id) & free0, m1 = __ballot(r1 == id) & free1;
+      int j = -1;
+      if (m1) {
+        j = 63 - __builtin_clzll(m1);
+        free1 &= ~(1ull << j);
+        j += 64;
+      } else if (m0) {
+        j = 63 - __builtin_clzll(m0);
+        free0 &= ~(1ull << j);
+      }
+      if (lane == 0) match[i] = j;
+    }
+    __syncthreads();
+    int m = 0, chunks = 0;
+    for (int i = lane; i < plen; i += 64) {
+      const int j = match[i];
+      if (j < 0) continue;
+      m += 1;
+      chunks += (i > 0 && j > 0 && match[i - 1] == j - 1) ? 0 : 1;
+    }
+    m = wave_sum(m);
+    chunks = wave_sum(chunks);
+    if (lane == 0) {
+      out[0] = m;
+      out[1] = chunks;
+    }
+    __syncthreads();  // match is rewritten for the next reference
+  }
+}
+
 }  // namespace
 }  // namespace pgca
 
@@ -297,4 +422,24 @@ extern "C" int pgca_token_overlap(const int64_t* a_ids, const int32_t* a_len, co
   hipLaunchKernelGGL(token_overlap_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, (const long long*)a_ids, a_len,
                      (const long long*)b_ids, b_len, S, out);
   return check_launch("pgca_token_overlap");
+}
+
+extern "C" int pgca_rouge_stats(const int64_t* pred_ids, const int32_t* pred_len, const int64_t* ref_ids,
+                                const int32_t* ref_len, int32_t N, int32_t K, int32_t S, int32_t base_vocab,
+                                int32_t* out, void* stream) {
+  REQUIRE(pred_ids && pred_len && ref_ids && ref_len && out, "pgca_rouge_stats");
+  EVAL_LIMITS("pgca_rouge_stats", N, K, S, base_vocab);
+  hipLaunchKernelGGL(rouge_stats_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, (const long long*)pred_ids,
+                     pred_len, (const long long*)ref_ids, ref_len, K, S, out);
+  return check_launch("pgca_rouge_stats");
+}
+
+extern "C" int pgca_meteor_stats(const int64_t* pred_ids, const int32_t* pred_len, const int64_t* ref_ids,
+                                 const int32_t* ref_len, int32_t N, int32_t K, int32_t S, int32_t base_vocab,
+                                 int32_t* out, void* stream) {
+  REQUIRE(pred_ids && pred_len && ref_ids && ref_len && out, "pgca_meteor_stats");
+  EVAL_LIMITS("pgca_meteor_stats", N, K, S, base_vocab);
+  hipLaunchKernelGGL(meteor_stats_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, (const long long*)pred_ids,
+                     pred_len, (const long long*)ref_ids, ref_len, K, S, out);
+  return check_launch("pgca_meteor_stats");
 }

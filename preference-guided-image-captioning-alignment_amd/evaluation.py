@@ -1,4 +1,5 @@
-"""Caption evaluation where the generated ids are: BLEU, CIDEr, diversity, preference win rate, alignment, latency.
+"""Caption evaluation where the generated ids are: BLEU, CIDEr, ROUGE, METEOR, diversity, preference win rate, alignment,
+latency.
 
 The reference scores decoded text on the host (evaluation/metrics.py: ``CaptioningMetrics``, ``EvaluationRunner``).  Here
 the same formulas run over TOKEN IDS in HIP (csrc/eval.hip), next to the ids ``generate_token_ids`` leaves on the device.
@@ -6,8 +7,10 @@ the same formulas run over TOKEN IDS in HIP (csrc/eval.hip), next to the ids ``g
 A "word" is a base-vocabulary token id.  The decoder's specials ([PAD], [BOS], [EOS]: ids >= ``arch.gpt.base_vocab``) are
 stripped first, by ``pgca_candidate_rows``, the conversion the mining scorer already uses.  The numbers are therefore the
 reference's formulas applied to BPE tokens: they track a model inside this project and are NOT comparable with the
-word-level BLEU / CIDEr of papers (a word is often several tokens, which raises n-gram precision and shortens the
-reach of a 4-gram).  ROUGE, METEOR, BERTScore and ``human_preference_correlation`` are not computed.
+word-level BLEU / CIDEr / ROUGE / METEOR of papers (a word is often several tokens, which raises n-gram precision and
+shortens the reach of a 4-gram).  ROUGE-1 / 2 / L and METEOR (exact-match stage: the stemmer and WordNet stages are the
+identity on ids) are the order-sensitive scores of the set: the longest common subsequence and METEOR's chunk penalty see
+word order beyond four tokens.  BERTScore and ``human_preference_correlation`` are not computed.
 
 ``ReferenceCorpus``  the stripped references of a loader and, per n-gram order, the sorted keys with their document
                      frequencies: built once, reused for every checkpoint or epoch; no generation runs.
@@ -161,6 +164,48 @@ def bleu_from_stats(stats: List[int], order: int) -> float:
     return geo * (1.0 if pred_len / ref_len > 1.0 else math.exp(1.0 - ref_len / pred_len))
 
 
+METEOR_ALPHA, METEOR_BETA, METEOR_GAMMA = 0.9, 3.0, 0.5   # HF ``meteor``'s defaults, which the reference takes
+
+
+def _harmonic(p: float, r: float) -> float:
+    return 2.0 * p * r / (p + r) if p + r > 0.0 else 0.0
+
+
+def rouge_from_stats(stats: List[List[int]]) -> Dict[str, float]:
+    """``rouge1`` / ``rouge2`` / ``rougeL`` from the six integers per image of ``pgca_rouge_stats`` (overlap_1, overlap_2,
+    lcs, pred_len, ref_len, k_used): per image F = 2PR / (P + R) with P = overlap_n / max(pred_len - n + 1, 1) and
+    R = overlap_n / max(ref_len - n + 1, 1), for ROUGE-L P = lcs / pred_len and R = lcs / ref_len (F = 0 when either
+    length is 0); then the mean over all images, one with no reference (k_used = -1) counting as 0."""
+    f1 = f2 = fl = 0.0
+    for o1, o2, lcs, pred_len, ref_len, k_used in ([int(v) for v in row] for row in stats):
+        if k_used < 0:
+            continue
+        f1 += _harmonic(o1 / max(pred_len, 1), o1 / max(ref_len, 1))
+        f2 += _harmonic(o2 / max(pred_len - 1, 1), o2 / max(ref_len - 1, 1))
+        if pred_len > 0 and ref_len > 0:
+            fl += _harmonic(lcs / pred_len, lcs / ref_len)
+    n = max(len(stats), 1)
+    return {"rouge1": f1 / n, "rouge2": f2 / n, "rougeL": fl / n}
+
+
+def meteor_from_stats(stats: List[List[List[int]]], pred_len: List[int], ref_len: List[List[int]]) -> float:
+    """``meteor`` from the [m, chunks] per reference of ``pgca_meteor_stats`` and the lengths: per reference
+    P = m / pred_len, R = m / ref_len, F = PR / (0.9 P + 0.1 R), score = (1 - 0.5 (chunks / m)^3) F (0 when m or a length
+    is 0); per image the best present reference (``ref_len`` >= 0); then the mean over all images."""
+    total = 0.0
+    for rows, plen, rlens in zip(stats, pred_len, ref_len):
+        best = 0.0
+        for (m, chunks), rlen in zip(rows, rlens):
+            m, chunks, plen, rlen = int(m), int(chunks), int(plen), int(rlen)
+            if rlen <= 0 or plen <= 0 or m <= 0:
+                continue
+            p, r = m / plen, m / rlen
+            f = p * r / (METEOR_ALPHA * p + (1.0 - METEOR_ALPHA) * r)
+            best = max(best, (1.0 - METEOR_GAMMA * (chunks / m) ** METEOR_BETA) * f)
+        total += best
+    return total / max(len(stats), 1)
+
+
 def _percentile(sorted_values: List[float], q: float) -> float:
     """numpy's default (linear) percentile of an ascending list."""
     pos = (len(sorted_values) - 1) * q / 100.0
@@ -176,7 +221,10 @@ class CaptionEvaluator:
     ``False`` no synchronise is added and no latency key is returned.
 
     Result keys - the reference's names where the quantity is the reference's: ``bleu_1`` .. ``bleu_4``, ``cider``
-    (mean per-image score x 10), ``diversity_1``, ``diversity_2``, ``unique_caption_ratio``; with ``rejected_ids`` in the
+    (mean per-image score x 10), ``rouge1``, ``rouge2``, ``rougeL`` (mean per-image F against the image's first present
+    reference, as the reference scores them), ``meteor`` (mean per-image best score over the present references, exact
+    matches only) - like BLEU and CIDEr over BPE ids, not comparable with word-level ROUGE / METEOR;
+    ``diversity_1``, ``diversity_2``, ``unique_caption_ratio``; with ``rejected_ids`` in the
     batches ``preference_win_rate``, ``avg_preferred_similarity``, ``avg_rejected_similarity``, ``preference_margin``;
     ``alignment_score`` / ``alignment_score_std`` (population std): the cosine of the model's own Stage-1 towers between
     image and generated caption - this project's stand-in for CLIP-Score, not CLIP-Score; ``latency_mean_ms``,
@@ -228,6 +276,8 @@ class CaptionEvaluator:
         pred_len = torch.zeros(N, dtype=I32, device=dev)
         score, flag = torch.zeros(N, dtype=F64, device=dev), torch.zeros(N, dtype=I32, device=dev)
         stats = torch.zeros(N, 10, dtype=I64, device=dev)
+        rouge = torch.zeros(N, 6, dtype=I32, device=dev)          # overlap_1, overlap_2, lcs, pred_len, ref_len, k_used
+        meteor = torch.zeros(N, K, 2, dtype=I32, device=dev)      # per reference: matches, chunks
         over = torch.zeros(2, N, 2, dtype=I32, device=dev)        # [preferred | rejected], image, [both, either]
         side_len = torch.zeros(2, N, dtype=I32, device=dev)
         align = torch.zeros(N, dtype=F32, device=dev)
@@ -256,6 +306,8 @@ class CaptionEvaluator:
                            corpus.table_keys, corpus.table_df, corpus.table_off, corpus.n_docs, self.sigma, score[rows],
                            flag[rows])
             hip.bleu_stats(pred_ids[rows], pred_len[rows], ref_ids[rows], ref_len[rows], B, K, S, base, stats[rows])
+            hip.rouge_stats(pred_ids[rows], pred_len[rows], ref_ids[rows], ref_len[rows], B, K, S, base, rouge[rows])
+            hip.meteor_stats(pred_ids[rows], pred_len[rows], ref_ids[rows], ref_len[rows], B, K, S, base, meteor[rows])
             pairs = "rejected_ids" in batch and "preferred_ids" in batch
             if has_pairs is not None and pairs != has_pairs:
                 raise ValueError("some batches carry preferred / rejected captions and some do not")
@@ -298,20 +350,25 @@ class CaptionEvaluator:
         # the one read-back
         packed = torch.cat([score, flag.to(F64), stats.to(F64).view(-1), over.to(F64).view(-1),
                             side_len.to(F64).view(-1), align.to(F64), pred_len.to(F64),
-                            torch.stack(div + [bad]).to(F64)]).cpu()
-        parts = torch.split(packed, [N, N, 10 * N, 4 * N, 2 * N, N, N, 6])
+                            torch.stack(div + [bad]).to(F64), rouge.to(F64).view(-1), meteor.to(F64).view(-1),
+                            ref_len.to(F64).view(-1)]).cpu()
+        parts = torch.split(packed, [N, N, 10 * N, 4 * N, 2 * N, N, N, 6, 6 * N, 2 * K * N, K * N])
         score_h, flag_h, align_h, len_h = parts[0], parts[1].long(), parts[5], parts[6].long()
         stats_h, over_h, side_h = parts[2].long().view(N, 10), parts[3].long().view(2, N, 2), parts[4].long().view(2, N)
         d1u, d1t, d2u, d2t, unique, n_bad = (int(v) for v in parts[7])
+        rouge_h, meteor_h = parts[8].long().view(N, 6), parts[9].long().view(N, K, 2)
+        ref_len_h = parts[10].long().view(N, K)
         if n_bad:
             raise ValueError(f"{n_bad} caption rows hold an id outside the decoder's or the text tower's vocabulary")
         if int(flag_h.sum()):
             raise ValueError(f"{int(flag_h.sum())} of {N} images have no reference")
         self.last = {"cider": score_h, "bleu_stats": stats_h, "overlap": over_h, "alignment": align_h, "length": len_h,
-                     "pred_ids": pred_ids.cpu()}
+                     "pred_ids": pred_ids.cpu(), "rouge_stats": rouge_h, "meteor_stats": meteor_h}
         total = [int(v) for v in stats_h.sum(0)]
         out: Dict[str, float] = {f"bleu_{n}": bleu_from_stats(total, n) for n in range(1, 5)}
         out["cider"] = float(score_h.sum() / N * 10.0)
+        out.update(rouge_from_stats(rouge_h.tolist()))
+        out["meteor"] = meteor_from_stats(meteor_h.tolist(), len_h.tolist(), ref_len_h.tolist())
         out["diversity_1"] = d1u / d1t if d1t else 0.0
         out["diversity_2"] = d2u / d2t if d2t else 0.0
         out["unique_caption_ratio"] = unique / N

@@ -449,6 +449,16 @@ def token_overlap(a_ids, a_len, b_ids, b_len, R, S, out):
     _call("pgca_token_overlap", a_ids, a_len, b_ids, b_len, R, S, out)
 
 
+def rouge_stats(pred_ids, pred_len, ref_ids, ref_len, N, K, S, base_vocab, out):
+    """``out`` int32 [N, 6]: overlap_1, overlap_2, lcs, pred_len, ref_len, k_used (first present reference, -1: none)."""
+    _call("pgca_rouge_stats", pred_ids, pred_len, ref_ids, ref_len, N, K, S, base_vocab, out)
+
+
+def meteor_stats(pred_ids, pred_len, ref_ids, ref_len, N, K, S, base_vocab, out):
+    """``out`` int32 [N, K, 2]: matches and chunks per reference, -1 / -1 for an absent one."""
+    _call("pgca_meteor_stats", pred_ids, pred_len, ref_ids, ref_len, N, K, S, base_vocab, out)
+
+
 def masked_mean_fwd(feats, mask, B, S, H, pooled, cu=None):
     _call("pgca_masked_mean_fwd", feats, mask, B, S, H, pooled, cu)
 
